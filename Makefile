@@ -46,9 +46,9 @@ sanitize:
 
 bench:
 ifeq ($(NGPUS),1)
-	$(PY) bench.py --gpus 1
+	$(PY) bench.py --gpus 1 --full
 else
-	$(PY) -m torch.distributed.run --nnodes=1 --nproc-per-node $(NGPUS) --master-addr 127.0.0.1 --master-port $(PORT) bench.py --gpus $(NGPUS)
+	$(PY) -m torch.distributed.run --nnodes=1 --nproc-per-node $(NGPUS) --master-addr 127.0.0.1 --master-port $(PORT) bench.py --gpus $(NGPUS) --full
 endif
 
 generate_random_data:

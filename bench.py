@@ -17,18 +17,23 @@ Launch (ref run_approx_coding.sh:47-49 starts every rank from one mpirun command
                                       GPU call) and exits with its status
   torchrun --nproc-per-node N bench.py --gpus N ...   used as is; WORLD_SIZE must equal N
 
+A plain run sets up, warms up, times --steps rounds, writes --dump-outputs DIR if asked and prints
+the result line.  Every other measurement below (marked *) is a run of its own after the headline
+and needs --full.
+
 Reported on rank 0 as ONE JSON line:
   value / ms_per_step     timed rounds (barrier + device sync on both sides, MAX over ranks)
-  host_driven_ms_per_step the same rounds driven by the host collector's real wait-for-k
-                          path (HIP-event instrumented run; equals the headline path at N > 1)
   hbm_distinct_TBps       distinct X bytes rank 0 streams per round / round time
   fraction_of_rows_used_in_decode   mean over rounds of the training rows whose partitions
                           reach the decoded gradient (AGC < 1; exact codes = 1)
-  iters_to_loss_floor     rounds until the AGC training loss reaches the COMMON target
-                          loss_target = naive (exact, uncoded GD) 100-round loss + 1 %
   ranks                   per-rank breakdown: hosted workers, transport, kernel / put /
-                          wait / decode+update microseconds (Trainer.rank_report)
-  straggler_virtual       N = 1: the paper's claim under the reference's straggler model -- naive,
+                          wait / decode+update microseconds (Trainer.rank_report; with --full from
+                          the instrumented run, plus the gradient kernel timed on its own)
+* host_driven_ms_per_step the same rounds driven by the host collector's real wait-for-k
+                          path (HIP-event instrumented run; equals the headline path at N > 1)
+* iters_to_loss_floor     rounds until the AGC training loss reaches the COMMON target
+                          loss_target = naive (exact, uncoded GD) 100-round loss + 1 %
+* straggler_virtual       N = 1: the paper's claim under the reference's straggler model -- naive,
                           AGC with the reference's drain and AGC with the lazy drain under
                           Exp(--straggler-mean-ms) virtual delays: Σtimeset, loop wall-clock, their
                           delay floors and wall-clock to the common loss target (virtual_straggler_block)
@@ -53,6 +58,16 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run everything else the benchmark measures: the instrumented "
+                         "host-driven rounds and the isolated gradient kernel, the N > 1 straggler / reference-"
+                         "topology / single-GPU runs, the convergence runs, the N = 1 virtual-straggler block and "
+                         "the reference CPU-equivalent ratio (--no-floor, --no-breakdown, --no-straggler and "
+                         "--no-single-ref narrow it).  Default: the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed rounds, write what the headline run returned for them as DIR/<name>.npy "
+                         "(float64): beta_last_step (beta after the last timed round) and beta_timed_steps (beta "
+                         "after each timed round); at most 64 MB in all, a larger array as a fixed seeded sample")
     ap.add_argument("--clock-warmup-ms", type=float, default=60.0,
                     help="untimed rounds ahead of the warmup rounds, about this long: the GPU's power management "
                          "slows the first ~20 ms of sustained gradient streaming by up to 20 %% (profiles/round3/clocks)")
@@ -303,7 +318,7 @@ def main(argv=None) -> int:
         out["config"]["release_form"] = trainer.release_form
         if a.share_partitions:
             out["config"]["share_partitions"] = True
-        ref = _ref_cpu_equiv()
+        ref = _ref_cpu_equiv() if a.full else None
         if ref and (a.n_rows, a.n_cols, a.workers, a.stragglers) == (ref["n_rows"], ref["n_cols"], ref["workers"],
                                                                        ref["stragglers"]):
             # reference per-iteration math on 8 host CPU threads (tools/reference_cpu_equiv.py);
@@ -313,13 +328,16 @@ def main(argv=None) -> int:
         if out["x_distinct_bytes_rank0"]:
             out["hbm_distinct_TBps"] = out["x_distinct_bytes_rank0"] / sec_per_iter / 1e12
         out["fraction_of_rows_used_in_decode"] = decode_row_fraction(sch, res.arrivals[w0:], Arrival)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, res.betaset, w0)
     reports = env.gather_objects(trainer.rank_report())
     trainer_shard = trainer.shard_mode
     kernel_iso = None
-    for r in range(env.world):  # one rank at a time: ranks may share a GPU (rehearsals)
-        if r == env.rank and trainer.local_msgs:
-            kernel_iso = trainer.time_local_grad()
-        env.barrier()
+    if a.full:
+        for r in range(env.world):  # one rank at a time: ranks may share a GPU (rehearsals)
+            if r == env.rank and trainer.local_msgs:
+                kernel_iso = trainer.time_local_grad()
+            env.barrier()
     kernel_iso = env.gather_objects(kernel_iso)
     free(trainer)
     del trainer, res
@@ -345,7 +363,7 @@ def main(argv=None) -> int:
         return res_, why_ is None
 
     # ---- 2. the same rounds host-driven, instrumented: real wait-for-k path + per-rank breakdown -----
-    if not a.no_breakdown:
+    if a.full and not a.no_breakdown:
         headline = reports
         # N > 1: device records too, for the worker half of the round chain (worker_round_start_latency)
         tr = Trainer(make_cfg(w0 + a.steps, device_loop="off", instrument=True, device_records=env.world > 1), env)
@@ -383,7 +401,7 @@ def main(argv=None) -> int:
     # every round (a device spin after its gradient, before its put: ref src/naive.py:141-148), and
     # AGC with a lazy drain (no wait for the tail, stale rounds skipped on the late rank) is timed
     # against naive (which must wait for every worker), each with and without the straggler.
-    if env.world > 1 and not a.no_straggler and not failures:
+    if a.full and env.world > 1 and not a.no_straggler and not failures:
         S, W = a.straggler_steps, a.workers
         late_rank = env.world - 1
         late_workers = [w for w in range(W) if w % env.world == late_rank]  # parallel/placement.py place_spread
@@ -449,7 +467,7 @@ def main(argv=None) -> int:
             out["straggler"] = straggler
 
     # ---- 2c. N > 1: the same problem on rank 0's GPU alone, in this job (the scaling denominator) --------
-    if env.world > 1 and a.single_ref and not failures:
+    if a.full and env.world > 1 and a.single_ref and not failures:
         single = single_gpu_reference(a, make_cfg, env, free, Trainer, clock_rounds)
         if env.is_master and isinstance(single, str):  # rank 0's solo run failed: recorded, not collective
             out["single_gpu_reference_failure"] = single
@@ -464,7 +482,7 @@ def main(argv=None) -> int:
                                          "value_tolerant": "message (the reference topology)"}
 
     # ---- 3. convergence: naive (exact GD) sets the common loss target, then the scheme -------------
-    if not a.no_floor and not failures:
+    if a.full and not a.no_floor and not failures:
         curves = {}
         for name, naive in (("naive", True), ("scheme", a.naive)):
             if name == "scheme" and a.naive:
@@ -510,7 +528,7 @@ def main(argv=None) -> int:
     # and AGC with the lazy drain (no wait for the tail, a worker still busy skips the stale round: the
     # replacement of the reference's send Cancel, ref src/coded.py:178-180) run one after another, each
     # for --floor-rounds rounds, and are compared on wall-clock to the common loss target.
-    if env.world == 1 and not a.no_straggler and not a.no_floor and not failures:
+    if a.full and env.world == 1 and not a.no_straggler and not a.no_floor and not failures:
         try:  # one process: nothing collective inside, so a failure here is this rank's alone
             blk = virtual_straggler_block(a, make_cfg, env, free, Trainer, evaluate,
                                           out.get("ms_per_step", 0.0) / 1e3 if env.is_master else 0.0)
@@ -756,6 +774,32 @@ def decode_row_fraction(scheme, arrivals_log, Arrival) -> float:
         parts = {p for key in used for p in seg[key]}
         fr.append(len(parts) / n)
     return float(np.mean(fr)) if fr else None
+
+
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # array data of one --dump-outputs directory (files: under 64 MB in all)
+
+
+def dump_outputs(dirpath: str, betaset: np.ndarray, first_timed: int) -> dict:
+    """--dump-outputs: what the caller of the timed path (Trainer.run) receives for the timed rounds, as
+    float64 .npy files: ``beta_last_step`` (beta after the last timed round, the state the run leaves)
+    and ``beta_timed_steps`` (beta after every timed round, one row each).  The problem, beta_0, the
+    tie-break permutations and the round count are fixed by the arguments, so two builds run with the
+    same arguments are comparable file for file.  An array over its share of the budget (a quarter
+    for the last step, the rest for the trajectory) is written as a sample of its flattened entries at
+    sorted indices drawn without replacement from RandomState(0): the same entries for the same shape.
+    Returns {name: entries written}."""
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {"beta_last_step": (betaset[-1], DUMP_BUDGET_BYTES // 4),
+              "beta_timed_steps": (betaset[first_timed:], DUMP_BUDGET_BYTES - DUMP_BUDGET_BYTES // 4)}
+    written = {}
+    for name, (x, budget) in arrays.items():
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        keep = budget // x.itemsize
+        if x.size > keep:
+            x = x.reshape(-1)[np.sort(np.random.RandomState(0).choice(x.size, keep, replace=False))]
+        np.save(os.path.join(dirpath, name + ".npy"), x)
+        written[name] = int(x.size)
+    return written
 
 
 def _ref_cpu_equiv():

@@ -9,7 +9,9 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TINY = ["--steps", "3", "--warmup", "1", "--n-rows", "2400", "--n-cols", "20", "--floor-rounds", "8"]
+# --full: these tests read what the benchmark measures after its headline (a plain run times the headline only)
+TINY = ["--full", "--steps", "3", "--warmup", "1", "--n-rows", "2400", "--n-cols", "20", "--floor-rounds", "8"]
+PLAIN = TINY[1:-2]
 
 
 def _env():
@@ -120,6 +122,63 @@ def test_bench_one_gpu_straggler_block(tmp_path):
     lz, nv = st["agc_lazy"]["wallclock_s_to_target"], st["naive"]["wallclock_s_to_target"]
     assert st["agc_lazy_beats_naive_to_target"] is (lz < nv)
     assert st["agc_lazy"]["speedup_to_target_vs_naive"] == pytest.approx(nv / lz)
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full the benchmark times its headline and nothing else: the result line keeps the headline
+    fields and carries none of the later runs' (host-driven rounds, isolated kernel, convergence, straggler
+    block, CPU-equivalent ratio).  --steps sets the timed rounds, and --dump-outputs writes beta after the
+    last timed round and after each of them as float64 .npy files that a second run with the same
+    arguments reproduces exactly (seeded data, beta_0 and tie-break permutations)."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        out, dump = tmp_path / f"{name}.json", tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *PLAIN, "--clock-warmup-ms",
+                            "0", "--dump-outputs", str(dump), "--json-out", str(out)],
+                           cwd=str(tmp_path), env=_env(), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        d = json.loads(out.read_text())
+        assert json.loads(r.stdout.strip().splitlines()[-1]) == d
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "s/iter" and d["higher_is_better"] is False
+        assert d["dtype"] == "fp64" and d["value"] > 0 and d["ms_per_step"] == pytest.approx(1e3 * d["value"])
+        assert d["metric"].startswith("wall-clock sec/iter")
+        assert 0 < d["fraction_of_rows_used_in_decode"] <= 1 and [x["rank"] for x in d["ranks"]] == [0]
+        for k in ("host_driven_ms_per_step", "loss_target", "iters_to_loss_floor", "straggler_virtual",
+                  "ref_cpu_equiv_s_per_iter", "subrun_failures"):
+            assert k not in d, k
+        assert "kernel_us_isolated" not in d["ranks"][0]
+        assert sorted(os.listdir(dump)) == ["beta_last_step.npy", "beta_timed_steps.npy"]
+        last, timed = np.load(dump / "beta_last_step.npy"), np.load(dump / "beta_timed_steps.npy")
+        assert last.dtype == timed.dtype == np.float64
+        assert last.shape == (20,) and timed.shape == (3, 20)  # n_cols; timed steps x n_cols
+        assert np.all(np.isfinite(timed)) and np.array_equal(timed[-1], last)
+        assert not np.array_equal(timed[0], timed[1])  # the rounds moved beta
+        dumps.append((last, timed))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+
+
+def test_dump_outputs_samples_an_array_over_its_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs keeps a directory under its byte budget: an array over its share is written as a
+    fixed sample of its entries (sorted indices from RandomState(0)), the same ones at every call."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8 * 400)
+    traj = np.arange(9 * 50, dtype=np.float64).reshape(9, 50)
+    n = bench.dump_outputs(str(tmp_path / "d"), traj, 2)
+    # shares: 100 entries for the last step (50 fit), 300 for the 7 x 50 of the timed rounds (sampled)
+    assert n == {"beta_last_step": 50, "beta_timed_steps": 300}
+    assert np.array_equal(np.load(tmp_path / "d" / "beta_last_step.npy"), traj[-1])
+    got = np.load(tmp_path / "d" / "beta_timed_steps.npy")
+    idx = np.sort(np.random.RandomState(0).choice(350, 300, replace=False))
+    assert got.dtype == np.float64 and np.array_equal(got, traj[2:].reshape(-1)[idx])
+    bench.dump_outputs(str(tmp_path / "e"), traj, 2)
+    assert np.array_equal(np.load(tmp_path / "e" / "beta_timed_steps.npy"), got)
+    assert sum(os.path.getsize(tmp_path / "d" / f) for f in os.listdir(tmp_path / "d")) <= 8 * 400 + 2 * 128
 
 
 def test_bench_subrun_failure_keeps_the_headline(tmp_path):

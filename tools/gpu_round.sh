@@ -6,7 +6,7 @@
 #
 #   tests    python -m pytest tests -m gpu (thread timeouts, so a hang names its test)
 #   smoke    __graft_entry__.smoke()
-#   bench    bench.py at N=1 (20 steps as the driver runs it, then 100 settled steps)
+#   bench    bench.py --full at N=1 (20 steps with every later run, then 100 settled steps without the floor runs)
 #   prec     the headline in fp32 and bf16 (20 steps)
 #   shapes   the heaviest rank's gradient at every N-GPU placement (tools/bench_rank_shapes.py)
 #   sweep    dense gradient shape sweep vs the copy ceiling (tools/bench_kernels.py --only sweep)
@@ -46,7 +46,7 @@ run() {  # run <seconds> <log> <cmd...>
   log "end $f rc=$rc"
   if [ $rc -ne 0 ]; then tail -30 "$OUT/$f"; exit $rc; fi
 }
-BENCH="python -u bench.py --no-floor"
+BENCH="python -u bench.py --full --no-floor"
 for s in "${STAGES[@]}"; do
   case "$s" in
     tests)
@@ -61,7 +61,7 @@ for s in "${STAGES[@]}"; do
     smoke)
       run 300 smoke.log python -c 'import __graft_entry__ as g; g.build(); g.smoke(); print("smoke ok")' ;;
     bench)
-      run 600 bench.log python -u bench.py && tail -1 "$OUT/bench.log" > "$OUT/bench.json"
+      run 600 bench.log python -u bench.py --full && tail -1 "$OUT/bench.log" > "$OUT/bench.json"
       run 600 bench100.log $BENCH --steps 100 --warmup 10 && tail -1 "$OUT/bench100.log" > "$OUT/bench100.json"
       cat "$OUT/bench.json" ;;
     prec)
@@ -134,7 +134,7 @@ for s in "${STAGES[@]}"; do
       python tools/pmc_summary.py "$OUT/pmcs" --by-kernel > "$OUT/pmcs_summary.json" ;;
     rehearse)
       for n in 2 4 8; do
-        run 600 "rehearse_$n.log" python -u bench.py --gpus $n --steps 20 --warmup 5 --no-floor \
+        run 600 "rehearse_$n.log" python -u bench.py --full --gpus $n --steps 20 --warmup 5 --no-floor \
           --json-out "$OUT/rehearse_$n.json"
       done ;;
     prof)
