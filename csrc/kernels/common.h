@@ -251,7 +251,23 @@ __device__ __forceinline__ double readlane_a(double x, int l) {
 // gradient:  g = sum_rows r * x_row.
 //   logistic (ref naive.py:137-139):  g = -X^T( ymod / (exp(y*z) + 1) )  ->  r = -ymod * sigmoid(-y z)
 //   least squares (ref naive.py:345-346): g = -2 X^T (y - z)                ->  r = -2 * c * (y - z)
-enum LossKind : int { kLogistic = 0, kLeastSquares = 1 };
+//   squared hinge (L2-SVM, labels +-1):   g = -2 X^T( c y max(0, 1 - y z) ) ->  r = -2 * c * y * max(0, 1 - y z)
+//     (continuous in z, so one fmax form serves the per-row, the branch-free and the hardware variants)
+enum LossKind : int { kLogistic = 0, kLeastSquares = 1, kSquaredHinge = 2 };
+
+// Runtime loss code -> compile-time LOSS.  f is called with a std::integral_constant<int, LOSS> and
+// returns a hipError_t; an unknown code launches nothing.  Every launcher dispatches through this, so
+// a further loss is one case here plus its branch in residual / loss_value.
+//   dispatch_loss(loss, [&](auto L) { return launch<T, A, decltype(L)::value>(...); });
+template <typename F>
+inline hipError_t dispatch_loss(int loss, F&& f) {
+  switch (loss) {
+    case kLogistic: return f(std::integral_constant<int, kLogistic>{});
+    case kLeastSquares: return f(std::integral_constant<int, kLeastSquares>{});
+    case kSquaredHinge: return f(std::integral_constant<int, kSquaredHinge>{});
+    default: return hipErrorInvalidValue;
+  }
+}
 
 template <typename A>
 __device__ __forceinline__ A sigmoid_neg(A t) {
@@ -277,6 +293,8 @@ template <int LOSS>
 __device__ __forceinline__ float residual_hw(float z, float y, float coef) {
   if constexpr (LOSS == kLogistic) {
     return -(coef * y) * sigmoid_neg_hw(y * z);
+  } else if constexpr (LOSS == kSquaredHinge) {
+    return -2.f * (coef * y) * fmaxf(0.f, 1.f - y * z);
   } else {
     return -2.f * coef * (y - z);
   }
@@ -290,6 +308,8 @@ __device__ __forceinline__ A residual_branchfree(A z, A y, A coef) {
     const A e = exp(-fabs(t));
     const A q = A(1) / (A(1) + e);
     return -(coef * y) * (t > A(0) ? e * q : q);
+  } else if constexpr (LOSS == kSquaredHinge) {
+    return A(-2) * (coef * y) * fmax(A(0), A(1) - y * z);
   } else {
     return A(-2) * coef * (y - z);
   }
@@ -299,8 +319,26 @@ template <int LOSS, typename A>
 __device__ __forceinline__ A residual(A z, A y, A coef) {
   if constexpr (LOSS == kLogistic) {
     return -(coef * y) * sigmoid_neg<A>(y * z);
+  } else if constexpr (LOSS == kSquaredHinge) {
+    return A(-2) * (coef * y) * fmax(A(0), A(1) - y * z);
   } else {
     return A(-2) * coef * (y - z);
+  }
+}
+
+// Per-element loss of the evaluation epilogues (label y, prediction p, both widened to fp64):
+//   logistic log(1 + exp(-y p)) (stable form), least squares (y - p)^2, squared hinge max(0, 1 - y p)^2.
+template <int LOSS>
+__device__ __forceinline__ double loss_value(double y, double p) {
+  if constexpr (LOSS == kLogistic) {
+    const double m = -y * p;
+    return (m > 0.0 ? m : 0.0) + log1p(exp(-fabs(m)));
+  } else if constexpr (LOSS == kSquaredHinge) {
+    const double m = fmax(0.0, 1.0 - y * p);
+    return m * m;
+  } else {
+    const double e = y - p;
+    return e * e;
   }
 }
 

@@ -8,8 +8,8 @@
 //   fp32 / bf16 X : v_mfma_f32_16x16x4_f32 (exact f32 products, bf16 widened on staging)
 // Tiling: 256-thread workgroup = 4 waves = 64 rows x (16*NT) columns of P; K staged
 // through LDS in 32-deep tiles (row stride padded to 34 elements: conflict-free
-// ds_read_b64 for the 16x4 fragment pattern).  The epilogue applies softplus(-y p) or
-// (y-p)^2, reduces over the 64 rows (lane shuffles + LDS), and adds one value per
+// ds_read_b64 for the 16x4 fragment pattern).  The epilogue applies softplus(-y p),
+// (y-p)^2 or max(0, 1 - y p)^2 (common.h loss_value), reduces over the 64 rows (lane shuffles + LDS), and adds one value per
 // column per workgroup into the fp64 loss vector; optionally P itself is written (the
 // test-set predictions feed the AUC).
 #include <cstdlib>
@@ -109,15 +109,7 @@ eval_gemm_loss(const T* __restrict__ X, long long ldx, long long n, int d,
         if (P) P[gr * R + j] = p;
         const double yy = static_cast<double>(y[gr]);
         const double pp = static_cast<double>(p);
-        double l;
-        if constexpr (LOSS == kLogistic) {
-          const double m = -yy * pp;  // log(1 + exp(m)), stable
-          l = (m > 0.0 ? m : 0.0) + log1p(exp(-fabs(m)));
-        } else {
-          const double e = yy - pp;
-          l = e * e;
-        }
-        s += l;
+        s += loss_value<LOSS>(yy, pp);
       }
     }
     s += __shfl_xor(s, 16, kWave);
@@ -239,15 +231,7 @@ eval_gemm_loss_v2(const T* __restrict__ X, long long ldx, long long n, int d,
           if (P) P[gr * R + j] = p;
           const double yy = static_cast<double>(y[gr]);
           const double pp = static_cast<double>(p);
-          double l;
-          if constexpr (LOSS == kLogistic) {
-            const double mm = -yy * pp;
-            l = (mm > 0.0 ? mm : 0.0) + log1p(exp(-fabs(mm)));
-          } else {
-            const double e = yy - pp;
-            l = e * e;
-          }
-          s += l;
+          s += loss_value<LOSS>(yy, pp);
         }
       }
     s += __shfl_xor(s, 16, kWave);
@@ -277,27 +261,25 @@ hipError_t eval_gemm_loss_launch(int x_dtype, int loss_kind, const void* X, long
     const dim3 grid2(static_cast<unsigned>((n + kBM2 - 1) / kBM2), ceil_div(R, 16 * kNT2));
 #define EH_EVAL2(T, A, L) \
   hipLaunchKernelGGL((eval_gemm_loss_v2<T, A, L>), grid2, block, 0, st, (const T*)X, ldx, n, d, (const A*)y, (const A*)B, ldb, R, loss, (A*)P)
-    if (x_dtype == 0) {
-      if (loss_kind == kLogistic) EH_EVAL2(double, double, kLogistic); else EH_EVAL2(double, double, kLeastSquares);
-    } else if (x_dtype == 1) {
-      if (loss_kind == kLogistic) EH_EVAL2(float, float, kLogistic); else EH_EVAL2(float, float, kLeastSquares);
-    } else {
-      if (loss_kind == kLogistic) EH_EVAL2(bf16_t, float, kLogistic); else EH_EVAL2(bf16_t, float, kLeastSquares);
-    }
+    return dispatch_loss(loss_kind, [&](auto L) {
+      constexpr int kL = decltype(L)::value;
+      if (x_dtype == 0) EH_EVAL2(double, double, kL);
+      else if (x_dtype == 1) EH_EVAL2(float, float, kL);
+      else EH_EVAL2(bf16_t, float, kL);
+      return hipGetLastError();
+    });
 #undef EH_EVAL2
-    return hipGetLastError();
   }
 #define EH_EVAL(T, A, L) \
   hipLaunchKernelGGL((eval_gemm_loss<T, A, NT, L>), grid, block, 0, st, (const T*)X, ldx, n, d, (const A*)y, (const A*)B, ldb, R, loss, (A*)P)
-  if (x_dtype == 0) {
-    if (loss_kind == kLogistic) EH_EVAL(double, double, kLogistic); else EH_EVAL(double, double, kLeastSquares);
-  } else if (x_dtype == 1) {
-    if (loss_kind == kLogistic) EH_EVAL(float, float, kLogistic); else EH_EVAL(float, float, kLeastSquares);
-  } else {
-    if (loss_kind == kLogistic) EH_EVAL(bf16_t, float, kLogistic); else EH_EVAL(bf16_t, float, kLeastSquares);
-  }
+  return dispatch_loss(loss_kind, [&](auto L) {
+    constexpr int kL = decltype(L)::value;
+    if (x_dtype == 0) EH_EVAL(double, double, kL);
+    else if (x_dtype == 1) EH_EVAL(float, float, kL);
+    else EH_EVAL(bf16_t, float, kL);
+    return hipGetLastError();
+  });
 #undef EH_EVAL
-  return hipGetLastError();
 }
 
 }  // namespace eh

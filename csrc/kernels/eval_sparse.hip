@@ -4,6 +4,7 @@
 // Reference (every engine's epilogue, ref src/naive.py:166-169,190-193; ref src/util.py:136-141):
 //   predy_i = X.dot(betaset[i])   (scipy CSR x dense, one round at a time)
 //   loss_i  = sum(log(1 + exp(-y * predy_i))) / n        or mean((y - predy_i)^2)
+//   (squared hinge, not in the reference: mean(max(0, 1 - y * predy_i)^2))
 // The reference's real datasets are one-hot encoded: every row has the same number of
 // non-zeros and every value is 1 (ref src/arrange_real_data.py), so a prediction row is a sum
 // of m gathered beta columns.
@@ -80,13 +81,7 @@ eval_csr_loss(const long long* __restrict__ row_ptr, const int* __restrict__ col
       if (j < R) {
         if (P) P[r * R + j] = p[c];
         const double pp = static_cast<double>(p[c]);
-        if constexpr (LOSS == kLogistic) {
-          const double m = -yy * pp;  // log(1 + exp(m)), stable
-          s[c] += (m > 0.0 ? m : 0.0) + log1p(exp(-fabs(m)));
-        } else {
-          const double d = yy - pp;
-          s[c] += d * d;
-        }
+        s[c] += loss_value<LOSS>(yy, pp);
       }
     }
   }
@@ -116,15 +111,14 @@ hipError_t eval_csr_loss_launch(int dtype, int loss_kind, const long long* row_p
   }
 #define EH_CSR_V(A, L) \
   if (vals) { EH_CSR_NC(A, L, true) } else { EH_CSR_NC(A, L, false) }
-  if (dtype == 0) {
-    if (loss_kind == kLogistic) { EH_CSR_V(double, kLogistic) } else { EH_CSR_V(double, kLeastSquares) }
-  } else {
-    if (loss_kind == kLogistic) { EH_CSR_V(float, kLogistic) } else { EH_CSR_V(float, kLeastSquares) }
-  }
+  return dispatch_loss(loss_kind, [&](auto L) {
+    constexpr int kL = decltype(L)::value;
+    if (dtype == 0) { EH_CSR_V(double, kL) } else { EH_CSR_V(float, kL) }
+    return hipGetLastError();
+  });
 #undef EH_CSR_V
 #undef EH_CSR_NC
 #undef EH_CSR
-  return hipGetLastError();
 }
 
 }  // namespace eh

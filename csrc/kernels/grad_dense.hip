@@ -1627,20 +1627,14 @@ hipError_t grad_dense_launch(int dtype, int loss, int cpl, const void* segs, con
                              const PutDesc* put, const int* gate) {
   const Segment* S = static_cast<const Segment*>(segs);
   const Task* Tk = static_cast<const Task*>(tasks);
-  hipError_t e = hipSuccess;
-  if (dtype == 0) {
-    e = loss == kLogistic
-            ? launch_fused_cpl<double, double, kLogistic>(cpl, S, Tk, ntasks, (const double*)beta, (double*)slab, ld, st, k, gate)
-            : launch_fused_cpl<double, double, kLeastSquares>(cpl, S, Tk, ntasks, (const double*)beta, (double*)slab, ld, st, k, gate);
-  } else if (dtype == 1) {
-    e = loss == kLogistic
-            ? launch_fused_cpl<float, float, kLogistic>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k, gate)
-            : launch_fused_cpl<float, float, kLeastSquares>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k, gate);
-  } else {
-    e = loss == kLogistic
-            ? launch_fused_cpl<bf16_t, float, kLogistic>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k, gate)
-            : launch_fused_cpl<bf16_t, float, kLeastSquares>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k, gate);
-  }
+  const hipError_t e = dispatch_loss(loss, [&](auto L) {
+    constexpr int kL = decltype(L)::value;
+    if (dtype == 0)
+      return launch_fused_cpl<double, double, kL>(cpl, S, Tk, ntasks, (const double*)beta, (double*)slab, ld, st, k, gate);
+    if (dtype == 1)
+      return launch_fused_cpl<float, float, kL>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k, gate);
+    return launch_fused_cpl<bf16_t, float, kL>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k, gate);
+  });
   if (e != hipSuccess) return e;
   if (dtype == 0) return slab_reduce_launch<double>((const double*)slab, slot_task_begin, (double*)part, (double*)G, nslots, ld, st, put, gate);
   return slab_reduce_launch<float>((const float*)slab, slot_task_begin, (float*)part, (float*)G, nslots, ld, st, put, gate);
@@ -1655,16 +1649,14 @@ hipError_t grad_dense_update_launch(int dtype, int loss, int cpl, const void* se
     if (up.slot[m] < 0 || up.slot[m] >= nslots) return hipErrorInvalidValue;
   const Segment* S = static_cast<const Segment*>(segs);
   const Task* Tk = static_cast<const Task*>(tasks);
-  hipError_t e;
-  if (dtype == 0)
-    e = loss == kLogistic ? launch_fused_cpl<double, double, kLogistic>(cpl, S, Tk, ntasks, (const double*)beta, (double*)slab, ld, st, k)
-                          : launch_fused_cpl<double, double, kLeastSquares>(cpl, S, Tk, ntasks, (const double*)beta, (double*)slab, ld, st, k);
-  else if (dtype == 1)
-    e = loss == kLogistic ? launch_fused_cpl<float, float, kLogistic>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k)
-                          : launch_fused_cpl<float, float, kLeastSquares>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k);
-  else
-    e = loss == kLogistic ? launch_fused_cpl<bf16_t, float, kLogistic>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k)
-                          : launch_fused_cpl<bf16_t, float, kLeastSquares>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k);
+  hipError_t e = dispatch_loss(loss, [&](auto L) {
+    constexpr int kL = decltype(L)::value;
+    if (dtype == 0)
+      return launch_fused_cpl<double, double, kL>(cpl, S, Tk, ntasks, (const double*)beta, (double*)slab, ld, st, k);
+    if (dtype == 1)
+      return launch_fused_cpl<float, float, kL>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k);
+    return launch_fused_cpl<bf16_t, float, kL>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k);
+  });
   if (e != hipSuccess) return e;
   const dim3 pgrid(ceil_div(ld, kWave), nslots, kSplits);
   const size_t lds = static_cast<size_t>(nslots) * kWave * (dtype == 0 ? 8 : 4);
@@ -1693,25 +1685,23 @@ hipError_t grad_dense_twopass_launch(int dtype, int loss, const void* segs, cons
   const Segment* S = static_cast<const Segment*>(segs);
   const Task* Tk = static_cast<const Task*>(tasks);
   const dim3 block(256);
-  if (dtype == 0) {
-    if (loss == kLogistic)
-      hipLaunchKernelGGL((rowdot_residual<double, double, kLogistic>), dim3(ntasks), block, 0, st, S, Tk, (const double*)beta, task_row_off, (double*)rbuf, ld, gate);
+  const hipError_t el = dispatch_loss(loss, [&](auto L) {
+    constexpr int kL = decltype(L)::value;
+    if (dtype == 0)
+      hipLaunchKernelGGL((rowdot_residual<double, double, kL>), dim3(ntasks), block, 0, st, S, Tk, (const double*)beta, task_row_off, (double*)rbuf, ld, gate);
+    else if (dtype == 1)
+      hipLaunchKernelGGL((rowdot_residual<float, float, kL>), dim3(ntasks), block, 0, st, S, Tk, (const float*)beta, task_row_off, (float*)rbuf, ld, gate);
     else
-      hipLaunchKernelGGL((rowdot_residual<double, double, kLeastSquares>), dim3(ntasks), block, 0, st, S, Tk, (const double*)beta, task_row_off, (double*)rbuf, ld, gate);
+      hipLaunchKernelGGL((rowdot_residual<bf16_t, float, kL>), dim3(ntasks), block, 0, st, S, Tk, (const float*)beta, task_row_off, (float*)rbuf, ld, gate);
+    return hipSuccess;
+  });
+  if (el != hipSuccess) return el;
+  if (dtype == 0)
     hipLaunchKernelGGL((xt_r_tiles<double, double>), dim3(ntasks, ceil_div(ld, 256 * 2)), block, 0, st, S, Tk, task_row_off, (const double*)rbuf, (double*)slab, ld, gate);
-  } else if (dtype == 1) {
-    if (loss == kLogistic)
-      hipLaunchKernelGGL((rowdot_residual<float, float, kLogistic>), dim3(ntasks), block, 0, st, S, Tk, (const float*)beta, task_row_off, (float*)rbuf, ld, gate);
-    else
-      hipLaunchKernelGGL((rowdot_residual<float, float, kLeastSquares>), dim3(ntasks), block, 0, st, S, Tk, (const float*)beta, task_row_off, (float*)rbuf, ld, gate);
+  else if (dtype == 1)
     hipLaunchKernelGGL((xt_r_tiles<float, float>), dim3(ntasks, ceil_div(ld, 256 * 4)), block, 0, st, S, Tk, task_row_off, (const float*)rbuf, (float*)slab, ld, gate);
-  } else {
-    if (loss == kLogistic)
-      hipLaunchKernelGGL((rowdot_residual<bf16_t, float, kLogistic>), dim3(ntasks), block, 0, st, S, Tk, (const float*)beta, task_row_off, (float*)rbuf, ld, gate);
-    else
-      hipLaunchKernelGGL((rowdot_residual<bf16_t, float, kLeastSquares>), dim3(ntasks), block, 0, st, S, Tk, (const float*)beta, task_row_off, (float*)rbuf, ld, gate);
+  else
     hipLaunchKernelGGL((xt_r_tiles<bf16_t, float>), dim3(ntasks, ceil_div(ld, 256 * 8)), block, 0, st, S, Tk, task_row_off, (const float*)rbuf, (float*)slab, ld, gate);
-  }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (dtype == 0) return slab_reduce_launch<double>((const double*)slab, slot_task_begin, (double*)part, (double*)G, nslots, ld, st, nullptr, gate);

@@ -546,31 +546,28 @@ hipError_t grad_mfma_launch(int loss, const Segment* segs, const Task* tasks, in
   size_t lds = 0;
   if (!mfma_geometry(ld, &rows, &pieces, &nstage, &lds)) return hipErrorInvalidValue;
   const bool pack = R <= 4 && g_mfma_pack;
-  if (pack && (g_mfma_stream == 3 || g_mfma_stream == 4) && rows == 32 && g_mfma_probe != 2) {  // (ld <= 1024)
-    auto kern = g_mfma_stream == 3 ? (loss == kLogistic ? grad_vring_mfma<kLogistic, 2> : grad_vring_mfma<kLeastSquares, 2>)
-                                   : (loss == kLogistic ? grad_vring_mfma<kLogistic, 3> : grad_vring_mfma<kLeastSquares, 3>);
-    constexpr int vlds = 2 * (kMfNW * kVrPieces * 1024 + 256) + kMfNW * 16 * 32 * 4 + 16 * 32 * 2;
-    static_assert(vlds <= 160 * 1024, "two stage buffers + partial Z + residuals");
+  return dispatch_loss(loss, [&](auto L) {
+    constexpr int kL = decltype(L)::value;
+    if (pack && (g_mfma_stream == 3 || g_mfma_stream == 4) && rows == 32 && g_mfma_probe != 2) {  // (ld <= 1024)
+      auto kern = g_mfma_stream == 3 ? grad_vring_mfma<kL, 2> : grad_vring_mfma<kL, 3>;
+      constexpr int vlds = 2 * (kMfNW * kVrPieces * 1024 + 256) + kMfNW * 16 * 32 * 4 + 16 * 32 * 2;
+      static_assert(vlds <= 160 * 1024, "two stage buffers + partial Z + residuals");
+      const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, vlds);
+      if (ea != hipSuccess) return ea;
+      hipLaunchKernelGGL(kern, dim3(ntasks / R), dim3(64 * kMfNW), vlds, st, segs, tasks, beta, slab, ld, R, gate,
+                         g_mfma_probe);
+      return hipGetLastError();
+    }
+    auto kern = pack ? (rows == 32 ? grad_staged_mfma<kL, 32, true> : grad_staged_mfma<kL, 16, true>)
+                     : (rows == 32 ? grad_staged_mfma<kL, 32, false> : grad_staged_mfma<kL, 16, false>);
     const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, vlds);
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
     if (ea != hipSuccess) return ea;
-    hipLaunchKernelGGL(kern, dim3(ntasks / R), dim3(64 * kMfNW), vlds, st, segs, tasks, beta, slab, ld, R, gate,
-                       g_mfma_probe);
+    hipLaunchKernelGGL(kern, dim3(ntasks / R), dim3(64 * kMfNW), lds, st, segs, tasks, beta, slab, ld, R, pieces,
+                       nstage, gate, g_mfma_probe);
     return hipGetLastError();
-  }
-  auto pick = [&](auto p32l, auto p32q, auto p16l, auto p16q) {
-    return rows == 32 ? (loss == kLogistic ? p32l : p32q) : (loss == kLogistic ? p16l : p16q);
-  };
-  auto kern = pack ? pick(grad_staged_mfma<kLogistic, 32, true>, grad_staged_mfma<kLeastSquares, 32, true>,
-                          grad_staged_mfma<kLogistic, 16, true>, grad_staged_mfma<kLeastSquares, 16, true>)
-                   : pick(grad_staged_mfma<kLogistic, 32, false>, grad_staged_mfma<kLeastSquares, 32, false>,
-                          grad_staged_mfma<kLogistic, 16, false>, grad_staged_mfma<kLeastSquares, 16, false>);
-  const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-  if (ea != hipSuccess) return ea;
-  hipLaunchKernelGGL(kern, dim3(ntasks / R), dim3(64 * kMfNW), lds, st, segs, tasks, beta, slab, ld, R, pieces,
-                     nstage, gate, g_mfma_probe);
-  return hipGetLastError();
+  });
 }
 
 }  // namespace eh

@@ -805,11 +805,12 @@ hipError_t grad_sparse_launch(int dtype, int loss, const SparseArgs& a, const vo
   } else {                                                           \
     if (a.vals) EH_ELLL(A_, L_, false, true) else EH_ELLL(A_, L_, false, false)    \
   }
-      if (dtype == 0) {
-        if (loss == kLogistic) { EH_ELLV(double, kLogistic) } else { EH_ELLV(double, kLeastSquares) }
-      } else {
-        if (loss == kLogistic) { EH_ELLV(float, kLogistic) } else { EH_ELLV(float, kLeastSquares) }
-      }
+      const hipError_t el = dispatch_loss(loss, [&](auto L) {
+        constexpr int kL = decltype(L)::value;
+        if (dtype == 0) { EH_ELLV(double, kL) } else { EH_ELLV(float, kL) }
+        return hipSuccess;
+      });
+      if (el != hipSuccess) return el;
 #undef EH_ELLV
 #undef EH_ELLL
     } else if (a.ell) {
@@ -822,28 +823,27 @@ hipError_t grad_sparse_launch(int dtype, int loss, const SparseArgs& a, const vo
     if (a.vals) hipLaunchKernelGGL((ell_rows<A_, L_, false, true>), grid, block, 0, st, a, (const A_*)beta, gate); \
     else hipLaunchKernelGGL((ell_rows<A_, L_, false, false>), grid, block, 0, st, a, (const A_*)beta, gate);      \
   }
-      if (dtype == 0) {
-        if (loss == kLogistic) { EH_ELL(double, kLogistic) } else { EH_ELL(double, kLeastSquares) }
-      } else {
-        if (loss == kLogistic) { EH_ELL(float, kLogistic) } else { EH_ELL(float, kLeastSquares) }
-      }
+      const hipError_t el = dispatch_loss(loss, [&](auto L) {
+        constexpr int kL = decltype(L)::value;
+        if (dtype == 0) { EH_ELL(double, kL) } else { EH_ELL(float, kL) }
+        return hipSuccess;
+      });
+      if (el != hipSuccess) return el;
 #undef EH_ELL
     } else {
       // lanes per CSR row: 8 (16 / 8 / 4 at kc_house 13.45 / 13.2 / 13.05 us, amazon 21.4 / 21.2 / 21.7,
       // covtype 96.7 / 82.7 / 89.0: profiles/round6/sparse/csr_lanes)
       constexpr int Gs = 8;
       const dim3 grid(static_cast<unsigned>((a.nrows * Gs + 255) / 256));
-      if (dtype == 0) {
-        if (loss == kLogistic)
-          hipLaunchKernelGGL((csr_rows<double, kLogistic, Gs>), grid, block, 0, st, a, (const double*)beta, gate);
+      const hipError_t el = dispatch_loss(loss, [&](auto L) {
+        constexpr int kL = decltype(L)::value;
+        if (dtype == 0)
+          hipLaunchKernelGGL((csr_rows<double, kL, Gs>), grid, block, 0, st, a, (const double*)beta, gate);
         else
-          hipLaunchKernelGGL((csr_rows<double, kLeastSquares, Gs>), grid, block, 0, st, a, (const double*)beta, gate);
-      } else {
-        if (loss == kLogistic)
-          hipLaunchKernelGGL((csr_rows<float, kLogistic, Gs>), grid, block, 0, st, a, (const float*)beta, gate);
-        else
-          hipLaunchKernelGGL((csr_rows<float, kLeastSquares, Gs>), grid, block, 0, st, a, (const float*)beta, gate);
-      }
+          hipLaunchKernelGGL((csr_rows<float, kL, Gs>), grid, block, 0, st, a, (const float*)beta, gate);
+        return hipSuccess;
+      });
+      if (el != hipSuccess) return el;
     }
   }
   if (a.ntiles > 0 && a.wg) {

@@ -28,7 +28,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("positional", nargs="*")
     g = p.add_argument_group("extensions (defaults reproduce the reference)")
     g.add_argument("--precision", default="fp64", choices=["fp64", "fp32", "bf16"])
-    g.add_argument("--loss", default="auto", choices=["auto", "logistic", "least_squares"])
+    g.add_argument("--loss", default="auto", choices=["auto", "logistic", "least_squares", "squared_hinge"])
     g.add_argument("--num-itrs", type=int, default=100)
     g.add_argument("--lr", type=float, default=10.0)
     g.add_argument("--lr-schedule", default="const", choices=["const", "invscaling", "exponential"],

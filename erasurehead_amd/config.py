@@ -44,7 +44,7 @@ class RunConfig:
 
     # ---- extensions -----------------------------------------------------------------
     precision: str = "fp64"  # fp64 | fp32 | bf16 worker compute (master state always fp64)
-    loss: str = "auto"  # auto (reference dispatch) | logistic | least_squares
+    loss: str = "auto"  # auto (reference dispatch) | logistic | least_squares | squared_hinge
     seed: Optional[int] = None  # beta_0 / B matrix seed (reference: unseeded)
     data: str = "files"  # files | synthetic (on-device generator, no files)
     data_seed: int = 0

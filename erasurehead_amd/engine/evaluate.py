@@ -5,6 +5,8 @@ Reference quirks reproduced unless ``fix_quirks``:
     ``range(2, n_procs-1)``), labels are the matching prefix of label.dat (ref :172);
   * linear-regression runs print but do not write result files (ref src/naive.py:413-417);
   * result names follow each scheme's (colliding) prefixes (codes/schemes.py).
+Squared-hinge runs (not in the reference) are scored and printed like logistic ones, and every result
+name carries the prefix ``sqhinge_`` so a run in the same data directory keeps the logistic files.
 """
 from __future__ import annotations
 
@@ -15,10 +17,13 @@ import numpy as np
 import torch
 
 from ..data import io as dio
-from ..models.losses import LOGISTIC
+from ..models.losses import SQUARED_HINGE, is_classification
 from ..ops.eval import auc_columns, loss_sums, predictions_and_loss
 from ..utils import report
 from .trainer import TrainResult, Trainer
+
+
+SQHINGE_PREFIX = "sqhinge_"  # result files of squared-hinge runs (next to the logistic names)
 
 
 @dataclass
@@ -76,16 +81,19 @@ def evaluate(trainer: Trainer, res: TrainResult, log=None, write: bool = True) -
     n_test = Xt.shape[0]
     training_loss = sums / max(1, n_train)
     testing_loss = tsum / max(1, n_test)
-    auc = auc_columns(yt, P) if kind == LOGISTIC else np.zeros(R)
+    classify = is_classification(kind)
+    auc = auc_columns(yt, P) if classify else np.zeros(R)
     if cfg.verbose:
         for i in range(R):
-            if kind == LOGISTIC:
+            if classify:
                 log(report.logistic_line(i, training_loss[i], testing_loss[i], auc[i], res.timeset[i]))
             else:
                 log(report.linear_line(i, training_loss[i], testing_loss[i], res.timeset[i]))
     files = None
-    if write and (kind == LOGISTIC or cfg.save_linear):
+    if write and (classify or cfg.save_linear):
         names = trainer.scheme.output_names(cfg.fix_quirks)
+        if kind == SQUARED_HINGE:
+            names = {k: SQHINGE_PREFIX + v for k, v in names.items()}
         data_dir = getattr(trainer.source, "data_dir", None) or cfg.input_dir
         files = report.write_results(dio.results_dir(data_dir), names, training_loss, testing_loss, auc,
                                      res.timeset, res.worker_timeset, cfg.full_precision_outputs)

@@ -50,7 +50,7 @@ from ..codes.schemes import Arrival, Scheme, SchemeError, make_scheme, scheme_ke
 from ..config import RunConfig
 from ..data import io as dio
 from ..data.source import DataSource, FileSource, SyntheticSource
-from ..models.losses import LEAST_SQUARES, LOGISTIC, UpdateRule
+from ..models.losses import LEAST_SQUARES, LOGISTIC, LOSS_NAMES, UpdateRule, is_classification
 from ..ops.grad import DenseGradPlan, SharedGradPlan, SparseGradPlan
 from ..ops.precision import get_precision
 from ..ops.update import combine_update
@@ -131,9 +131,9 @@ class Trainer:
 
     # ------------------------------------------------------------------------------ setup
     def _start_eval_warmup(self):
-        """Master on a GPU, logistic runs that will be evaluated: load the AUC path's code objects on a
+        """Master on a GPU, classification runs (logistic, squared hinge) that will be evaluated: load the AUC path's code objects on a
         side thread while the data is generated / loaded (ops/eval.warm_auc; 0.6 s cold)."""
-        if not (self.env.is_master and self.env.gpu and self.cfg.evaluate and self.loss == LOGISTIC):
+        if not (self.env.is_master and self.env.gpu and self.cfg.evaluate and is_classification(self.loss)):
             return None
         import threading
 
@@ -171,7 +171,9 @@ class Trainer:
         if cfg.loss == "auto":
             self.loss = LEAST_SQUARES if (cfg.dataset == "kc_house_data" and scheme.has_linear) else LOGISTIC
         else:
-            self.loss = LEAST_SQUARES if cfg.loss == "least_squares" else LOGISTIC
+            if cfg.loss not in LOSS_NAMES:
+                raise ValueError(f"unknown loss {cfg.loss!r}: auto or one of {sorted(LOSS_NAMES)}")
+            self.loss = LOSS_NAMES[cfg.loss]
         self.rule_kind, self.rule_k = scheme.rule()
         self.update = UpdateRule("AGD" if scheme.fixed_agd else cfg.update_rule, cfg.alpha_value, cfg.n_rows,
                                  scheme.grad_scale())

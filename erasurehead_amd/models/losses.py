@@ -1,16 +1,18 @@
-"""Model math: logistic regression (L2) and least squares — fp64 NumPy oracles.
+"""Model math: logistic regression (L2), least squares and the squared-hinge L2-SVM — fp64 NumPy oracles.
 
 These are the reference formulas verbatim (SURVEY §2.2 "Math spec"), kept independent
 of the device path so the HIP kernels can be checked against them:
 
   logistic worker gradient   g = -X^T( y_mod / (exp(y * (X beta)) + 1) )   ref src/naive.py:137-139
   least-squares gradient     g = -2 X^T (y - X beta)                        ref src/naive.py:345-346
+  squared-hinge gradient     g = -2 X^T( y_mod * max(0, 1 - y * (X beta)) )  (L2-SVM; not in the reference)
   GD                         beta <- (1 - 2 alpha eta) beta - (eta/n) g      ref src/naive.py:112-115
   AGD (theta = 2/(i+2))      y = (1-theta) beta + theta u
                              beta' = y - (eta/n) g - 2 alpha eta beta
                              u = beta + (beta' - beta)/theta                 ref src/naive.py:116-122
   training loss              (1/n) sum log(1 + exp(-y * p))                 ref src/util.py:136-137
   MSE                        mean (y - p)^2                                  ref src/util.py:139-141
+  squared-hinge loss         mean max(0, 1 - y * p)^2
   AUC                        area under ROC of scores p vs labels in {-1,1}  ref src/naive.py:196-197
 """
 from __future__ import annotations
@@ -22,7 +24,13 @@ import numpy as np
 
 LOGISTIC = 0
 LEAST_SQUARES = 1
-LOSS_NAMES = {"logistic": LOGISTIC, "least_squares": LEAST_SQUARES}
+SQUARED_HINGE = 2
+LOSS_NAMES = {"logistic": LOGISTIC, "least_squares": LEAST_SQUARES, "squared_hinge": SQUARED_HINGE}
+
+
+def is_classification(kind: int) -> bool:
+    """Losses over labels in {-1, +1}: their runs are scored by ROC AUC and write result files."""
+    return kind in (LOGISTIC, SQUARED_HINGE)
 
 
 def _sigmoid_neg(t: np.ndarray) -> np.ndarray:
@@ -50,8 +58,21 @@ def least_squares_grad(X, y: np.ndarray, beta: np.ndarray, coef=None) -> np.ndar
     return np.asarray(X.T.dot(r)).ravel()
 
 
+def squared_hinge_grad(X, y: np.ndarray, beta: np.ndarray, coef=None) -> np.ndarray:
+    """-2 X^T (coef*y * max(0, 1 - y * X beta)); X dense ndarray or scipy sparse."""
+    z = X.dot(beta)
+    ymod = y if coef is None else coef * y
+    r = -2.0 * ymod * np.maximum(0.0, 1.0 - y * z)
+    return np.asarray(X.T.dot(r)).ravel()
+
+
+_GRADS = {LOGISTIC: logistic_grad, LEAST_SQUARES: least_squares_grad, SQUARED_HINGE: squared_hinge_grad}
+
+
 def worker_grad(kind: int, X, y, beta, coef=None) -> np.ndarray:
-    return logistic_grad(X, y, beta, coef) if kind == LOGISTIC else least_squares_grad(X, y, beta, coef)
+    if kind not in _GRADS:
+        raise ValueError(f"unknown loss kind {kind}")
+    return _GRADS[kind](X, y, beta, coef)
 
 
 def logistic_loss(y: np.ndarray, p: np.ndarray, n: Optional[int] = None) -> float:
@@ -59,6 +80,12 @@ def logistic_loss(y: np.ndarray, p: np.ndarray, n: Optional[int] = None) -> floa
     m = -np.asarray(y) * np.asarray(p)
     v = np.maximum(m, 0.0) + np.log1p(np.exp(-np.abs(m)))
     return float(v.sum() / (len(y) if n is None else n))
+
+
+def squared_hinge_loss(y: np.ndarray, p: np.ndarray, n: Optional[int] = None) -> float:
+    """(1/n) sum max(0, 1 - y p)^2."""
+    m = np.maximum(0.0, 1.0 - np.asarray(y, dtype=np.float64) * np.asarray(p, dtype=np.float64))
+    return float((m * m).sum() / (len(m) if n is None else n))
 
 
 def mse(y: np.ndarray, p: np.ndarray) -> float:

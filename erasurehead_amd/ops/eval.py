@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from .._ext import native
-from ..models.losses import LOGISTIC
+from ..models.losses import LEAST_SQUARES, LOGISTIC, SQUARED_HINGE
 
 
 def _loss_torch(kind: int, y: torch.Tensor, P: torch.Tensor) -> torch.Tensor:
@@ -27,6 +27,11 @@ def _loss_torch(kind: int, y: torch.Tensor, P: torch.Tensor) -> torch.Tensor:
     if kind == LOGISTIC:
         m = -y * P
         return (torch.clamp(m, min=0) + torch.log1p(torch.exp(-m.abs()))).sum(0)
+    if kind == SQUARED_HINGE:
+        m = torch.clamp(1.0 - y * P, min=0)
+        return (m * m).sum(0)
+    if kind != LEAST_SQUARES:
+        raise ValueError(f"unknown loss kind {kind}")
     e = y - P
     return (e * e).sum(0)
 

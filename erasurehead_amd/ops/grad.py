@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from .._ext import native
-from ..models.losses import LOGISTIC
+from ..models.losses import LEAST_SQUARES, LOGISTIC, SQUARED_HINGE
 from .precision import Precision
 
 _SEG = struct.Struct("<QQdq")  # csrc Segment {const void* X; const void* y; double coef; long long nrows}
@@ -394,6 +394,10 @@ def replica_dispatch_order(keys: Sequence[Tuple[int, int]], stride: int = 0) -> 
 def _residual_torch(kind: int, z, y, coef):
     if kind == LOGISTIC:
         return -(coef * y) * torch.sigmoid(-(y * z))
+    if kind == SQUARED_HINGE:
+        return -2.0 * (coef * y) * torch.clamp(1.0 - y * z, min=0)
+    if kind != LEAST_SQUARES:
+        raise ValueError(f"unknown loss kind {kind}")
     return -2.0 * coef * (y - z)
 
 
@@ -1058,8 +1062,12 @@ class SparseGradPlan:
                 z = A.dot(b)
                 if self.loss == LOGISTIC:
                     r = -(c * y) * (1.0 / (1.0 + np.exp(np.clip(y * z, -700, 700))))
-                else:
+                elif self.loss == SQUARED_HINGE:
+                    r = -2.0 * (c * y) * np.maximum(0.0, 1.0 - y * z)
+                elif self.loss == LEAST_SQUARES:
                     r = -2.0 * c * (y - z)
+                else:
+                    raise ValueError(f"unknown loss kind {self.loss}")
                 g += np.asarray(A.T.dot(r)).ravel()
             G[slot, : self.d] = torch.from_numpy(g).to(G.dtype)
         return G

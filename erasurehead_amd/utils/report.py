@@ -3,7 +3,7 @@
   ---- Starting <Scheme> Iterations ... ----
   \t >>> At Iteration <i>                       (every 10 rounds)
   Total Time Elapsed: %.3f
-  Iteration %d: Train Loss = %5.3f, Test Loss = %5.3f, AUC = %5.3f, Total time taken =%5.3f   (logistic)
+  Iteration %d: Train Loss = %5.3f, Test Loss = %5.3f, AUC = %5.3f, Total time taken =%5.3f   (logistic, squared hinge)
   Iteration %d: Train Loss = %.6f, Test Loss = %.6f, Total time taken =%5.3f                  (least squares)
   >>> Done
 ref src/naive.py:86,93,156,198,209 and :407; files via ref src/util.py:26-36.
