@@ -253,7 +253,9 @@ __device__ __forceinline__ double readlane_a(double x, int l) {
 //   least squares (ref naive.py:345-346): g = -2 X^T (y - z)                ->  r = -2 * c * (y - z)
 //   squared hinge (L2-SVM, labels +-1):   g = -2 X^T( c y max(0, 1 - y z) ) ->  r = -2 * c * y * max(0, 1 - y z)
 //     (continuous in z, so one fmax form serves the per-row, the branch-free and the hardware variants)
-enum LossKind : int { kLogistic = 0, kLeastSquares = 1, kSquaredHinge = 2 };
+//   softmax (multi-class, labels = class indices): its own kernel (grad_softmax.hip); the code is listed
+//     here for documentation only -- no scalar-residual kernel can run it, so dispatch_loss rejects it
+enum LossKind : int { kLogistic = 0, kLeastSquares = 1, kSquaredHinge = 2, kSoftmax = 3 };
 
 // Runtime loss code -> compile-time LOSS.  f is called with a std::integral_constant<int, LOSS> and
 // returns a hipError_t; an unknown code launches nothing.  Every launcher dispatches through this, so

@@ -121,6 +121,22 @@ constexpr int kSparseMaxDst = 4;
 hipError_t grad_sparse_launch(int dtype, int loss, const SparseArgs& a, const void* beta, hipStream_t st,
                               const int* gate = nullptr);
 
+// ---- multi-class softmax gradient (grad_softmax.hip) ----------------------------------------
+// Gb[p] = gradient of partition p's cross-entropy sum with coefficient 1, for every distinct local
+// partition in one pass over X: model beta and every Gb row are class-major [classes][ld_x] (D =
+// classes * ld_x elements), labels are class indices held as floats.  dtype 0 fp64 / 1 fp32,
+// 2 <= classes <= 8, ld_x <= 1024.  segs / tasks: the dense task table (grad_dense.h Segment / Task;
+// Task::slot = partition row of Gb, Task::slab = the task's index), tasks of one partition contiguous
+// and part_task_begin [nparts + 1] their ranges.  slab: [ntasks][kSoftmaxSubs][D] per-wave partial
+// sums (acc dtype), summed in a fixed order by the launch's second kernel; padding columns
+// [d_x, ld_x) of every class block of Gb are written as exact zeros.
+constexpr int kSoftmaxSubs = 4;
+constexpr int kSoftmaxMaxClasses = 8;
+constexpr int kSoftmaxMaxLd = 1024;
+hipError_t grad_softmax_launch(int dtype, int classes, const void* segs, const void* tasks, int ntasks,
+                               const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb,
+                               int d_x, int ld_x, hipStream_t st, const int* gate = nullptr);
+
 // layout probes of the bf16 MFMA gradient (grad_mfma.hip): one 16x16x32 product; one transposing read
 hipError_t mfma_probe_launch(const float* A, const float* B, float* C, hipStream_t st);
 hipError_t tr_probe_launch(const float* tile, int rowlen, float* out, hipStream_t st);

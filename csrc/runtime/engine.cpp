@@ -100,7 +100,7 @@ void need_gpu(const Tensor& t, const char* name) {
 // Python plan (ops/grad.py).  The plan object keeps every referenced tensor alive; the
 // launcher also holds references.
 struct GradLauncher {
-  int kind = 0;  // 0 dense fused, 1 dense two-pass, 2 sparse
+  int kind = 0;  // 0 dense fused, 1 dense two-pass, 2 sparse, 3 multi-class softmax
   int dtype = 0, loss = 0, cpl = 0, ntasks = 0, nslots = 0, ld = 0;
   eh::KernelChoice choice{};
   const void* segs = nullptr;
@@ -112,6 +112,9 @@ struct GradLauncher {
   void* rbuf = nullptr;
   int acc = 0;
   eh::SparseArgs sa{};  // kind 2 (grad_sparse.hip); Gb is the launch's output
+  // kind 3 (grad_softmax.hip): classes, data columns / row stride (ld is the flattened classes * ld_x),
+  // distinct partitions (the rows the kernel writes) and their task ranges stb [nparts + 1]
+  int classes = 0, d_x = 0, ld_x = 0, nparts = 0;
   // optional device encoding (csrc/kernels/encode.hip): the kernels above write the distinct
   // partitions' gradients into Gb, then G[slot] = sum_k coef * Gb[idx] for the enc_slots messages
   void* Gb = nullptr;
@@ -168,6 +171,9 @@ struct GradLauncher {
         if (!a.sub_begin) a.Gs = G;  // no sub-blocks: pass 2 / 3 write the partitions directly
         return eh::grad_sparse_launch(acc, loss, a, beta, st, gate);
       }
+      case 3:
+        return eh::grad_softmax_launch(dtype, classes, segs, tasks, ntasks, stb, nparts, beta, slab, G, d_x, ld_x, st,
+                                       gate);
       default:
         return hipErrorInvalidValue;
     }
@@ -213,6 +219,43 @@ std::shared_ptr<GradLauncher> make_dense(int64_t dtype, int64_t loss, int64_t cp
          "cpl (narrow: columns per lane, wide: block size) must cover ld");
     g->kind = 0;
   }
+  return g;
+}
+
+// Softmax plan (ops/softmax.py SoftmaxGradPlan): every distinct local partition once with coefficient 1
+// into rows of classes * ld_x elements; the plan's device encoding (set_encode) forms the messages unless
+// they are exactly the partitions.
+std::shared_ptr<GradLauncher> make_softmax(int64_t dtype, int64_t classes, const Tensor& segs, const Tensor& tasks,
+                                           const Tensor& slab, const Tensor& part_task_begin, int64_t d_x,
+                                           int64_t ld_x) {
+  for (auto* t : {&segs, &tasks, &slab, &part_task_begin}) need_gpu(*t, "softmax plan operand");
+  need(dtype == 0 || dtype == 1, "softmax: fp64 or fp32 storage");
+  need(classes >= 2 && classes <= eh::kSoftmaxMaxClasses, "softmax: classes must be in 2..8");
+  need(ld_x >= 1 && ld_x <= eh::kSoftmaxMaxLd && d_x >= 1 && d_x <= ld_x && ld_x % (dtype == 0 ? 2 : 4) == 0,
+       "softmax: rows of at most 1024 columns, padded to the 16-byte vector width");
+  need(tasks.dim() == 2 && tasks.size(1) == 5 && tasks.scalar_type() == at::kInt, "tasks must be int32 [n,5]");
+  need(segs.scalar_type() == at::kByte && segs.numel() % 32 == 0, "segs must be packed uint8 [nseg*32]");
+  need(part_task_begin.scalar_type() == at::kInt && part_task_begin.numel() >= 1, "part_task_begin must be int32");
+  auto g = std::make_shared<GradLauncher>();
+  g->kind = 3;
+  g->dtype = (int)dtype;
+  g->acc = (int)dtype;
+  g->loss = 3;
+  g->classes = (int)classes;
+  g->d_x = (int)d_x;
+  g->ld_x = (int)ld_x;
+  g->ld = (int)(classes * ld_x);
+  g->ntasks = (int)tasks.size(0);
+  g->nparts = (int)part_task_begin.numel() - 1;
+  g->nslots = g->nparts;
+  need(acc_code(slab) == g->acc &&
+           slab.numel() >= (int64_t)std::max(1, g->ntasks) * eh::kSoftmaxSubs * g->ld,
+       "slab must hold [ntasks][4][classes * ld_x] partial sums (acc dtype)");
+  g->segs = segs.data_ptr();
+  g->tasks = tasks.data_ptr();
+  g->slab = slab.data_ptr();
+  g->stb = part_task_begin.data_ptr<int>();
+  g->keep = {segs, tasks, slab, part_task_begin};
   return g;
 }
 
@@ -2210,6 +2253,8 @@ void bind_engine(py::module& m) {
                   py::arg("tasks"), py::arg("slab"), py::arg("slot_task_begin"), py::arg("part"), py::arg("ld"),
                   py::arg("task_row_off") = py::none(), py::arg("rbuf") = py::none(),
                   py::arg("choice") = eh::KernelChoice{})
+      .def_static("softmax", &make_softmax, py::arg("dtype"), py::arg("classes"), py::arg("segs"), py::arg("tasks"),
+                  py::arg("slab"), py::arg("part_task_begin"), py::arg("d_x"), py::arg("ld_x"))
       .def_static("sparse", &make_sparse, py::arg("loss"), py::arg("y"), py::arg("u"), py::arg("ell_idx"), py::arg("lo"),
                   py::arg("row_ptr"), py::arg("col_idx"), py::arg("vals"), py::arg("crow"), py::arg("cvals"),
                   py::arg("col_ptr"), py::arg("tiles"), py::arg("part_entry0"), py::arg("part_row0"),

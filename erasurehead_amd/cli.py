@@ -18,6 +18,7 @@ import sys
 from typing import List, Optional
 
 from .config import RunConfig
+from .models.losses import LOSS_CHOICES
 
 USAGE = ("Usage: python main.py n_procs n_rows n_cols input_dir is_real dataset is_coded n_stragglers "
          "partial_straggler_partitions coded_ver num_itrs")  # verbatim (stale) reference usage line, ref main.py:21
@@ -28,7 +29,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("positional", nargs="*")
     g = p.add_argument_group("extensions (defaults reproduce the reference)")
     g.add_argument("--precision", default="fp64", choices=["fp64", "fp32", "bf16"])
-    g.add_argument("--loss", default="auto", choices=["auto", "logistic", "least_squares", "squared_hinge"])
+    g.add_argument("--loss", default="auto", choices=["auto", *LOSS_CHOICES])
+    g.add_argument("--classes", type=int, default=None,
+                   help="--loss softmax: number of classes, 2..8 (default 2); labels are class indices 0..C-1")
     g.add_argument("--num-itrs", type=int, default=100)
     g.add_argument("--lr", type=float, default=10.0)
     g.add_argument("--lr-schedule", default="const", choices=["const", "invscaling", "exponential"],
@@ -108,7 +111,7 @@ def parse(argv: List[str]):
     cfg = RunConfig(int(n_procs), int(n_rows), int(n_cols), input_dir, int(is_real), dataset, int(is_coded),
                     int(n_stragglers), int(partitions), int(coded_ver), int(num_collect), int(add_delay),
                     update_rule, num_itrs=a.num_itrs, alpha=a.alpha, lr=a.lr,
-                    lr_kind=a.lr_schedule, lr_t0=a.lr_t0, lr_decay=a.lr_decay, precision=a.precision, loss=a.loss,
+                    lr_kind=a.lr_schedule, lr_t0=a.lr_t0, lr_decay=a.lr_decay, precision=a.precision, loss=a.loss, classes=a.classes,
                     seed=a.seed, data=a.data, data_seed=a.data_seed, allow_uneven_groups=a.allow_uneven_groups,
                     drain=a.drain, delay_mode=a.delay_mode, fixed_stragglers=a.fixed_stragglers,
                     fixed_sleep=a.fixed_sleep, kill_workers=a.kill_workers, force_delay=a.force_delay,

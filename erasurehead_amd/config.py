@@ -44,7 +44,8 @@ class RunConfig:
 
     # ---- extensions -----------------------------------------------------------------
     precision: str = "fp64"  # fp64 | fp32 | bf16 worker compute (master state always fp64)
-    loss: str = "auto"  # auto (reference dispatch) | logistic | least_squares | squared_hinge
+    loss: str = "auto"  # auto (reference dispatch) | logistic | least_squares | squared_hinge | softmax
+    classes: Optional[int] = None  # softmax only: number of classes, 2..8 (default 2)
     seed: Optional[int] = None  # beta_0 / B matrix seed (reference: unseeded)
     data: str = "files"  # files | synthetic (on-device generator, no files)
     data_seed: int = 0
@@ -115,6 +116,12 @@ class RunConfig:
             raise ValueError("delay_on must be collector or worker")
         if self.drain not in (None, "all", "carry", "lazy"):
             raise ValueError("drain must be all, carry or lazy")
+        if self.loss == "softmax":
+            self.classes = 2 if self.classes is None else int(self.classes)
+            if not 2 <= self.classes <= 8:
+                raise ValueError(f"classes must be in 2..8, got {self.classes}")
+        elif self.classes is not None:
+            raise ValueError(f"classes is an option of the softmax loss, not of {self.loss!r}")
         if any(int(f) < 1 for f in self.slow_ranks.values()):
             raise ValueError("slow rank factors must be integers >= 1")
 

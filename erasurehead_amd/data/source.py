@@ -92,8 +92,8 @@ class FileSource(DataSource):
 class SyntheticSource(DataSource):
     """Partitions of the reference synthetic model generated on the device (no files)."""
 
-    def __init__(self, n_rows: int, n_cols: int, n_partitions: int, seed: int = 0):
-        self.gen = DeviceGMM(n_rows, n_cols, n_partitions, seed)
+    def __init__(self, n_rows: int, n_cols: int, n_partitions: int, seed: int = 0, classes: Optional[int] = None):
+        self.gen = DeviceGMM(n_rows, n_cols, n_partitions, seed, classes=classes)
         self.d = n_cols
 
     def partition(self, p, prec, device):

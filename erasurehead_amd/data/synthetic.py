@@ -85,13 +85,18 @@ def synthetic_dir(output_dir: str, n_procs: int, n_rows: int, n_cols: int, n_str
 
 @dataclass
 class DeviceGMM:
-    """Deterministic on-device generator of the reference's synthetic model."""
+    """Deterministic on-device generator of the reference's synthetic model.
+
+    classes = C (multi-class softmax runs): C random +-1 vectors B*, rows from a C-component mixture
+    with means (1.5 / d) B*_c and labels 0..C-1 drawn from Categorical(softmax(X B*^T)).  classes =
+    None: the binary model, every draw bit-for-bit as without the argument."""
 
     n_rows: int
     n_cols: int
     n_partitions: int
     seed: int = 0
     ld: Optional[int] = None
+    classes: Optional[int] = None
 
     def __post_init__(self):
         if self.n_rows % self.n_partitions:
@@ -100,6 +105,8 @@ class DeviceGMM:
         self.beta_star = random_binvec(self.n_cols, rng).astype(np.float64)
         if self.ld is None:
             self.ld = self.n_cols
+        if self.classes is not None:
+            self.B_star = np.stack([random_binvec(self.n_cols, rng) for _ in range(int(self.classes))]).astype(np.float64)
 
     @property
     def rows_per_partition(self) -> int:
@@ -110,6 +117,8 @@ class DeviceGMM:
 
         d = self.n_cols
         host = np.random.RandomState((self.seed * 1000003 + stream * 7919 + 17) % (2 ** 31))
+        if self.classes is not None:
+            return self._draw_classes(n, host, device, dtype)
         c2 = int(host.binomial(n, 0.5))
         c1 = n - c2
         gen = torch.Generator(device=device)
@@ -124,6 +133,23 @@ class DeviceGMM:
         body[c1:].sub_(mu)
         prob = torch.sigmoid(body @ bstar)
         y = 2.0 * torch.bernoulli(prob, generator=gen) - 1.0
+        return X.to(dtype) if dtype != torch.float64 else X, y
+
+    def _draw_classes(self, n: int, host, device, dtype):
+        import torch
+
+        d, C = self.n_cols, int(self.classes)
+        comp = torch.as_tensor(host.randint(0, C, size=n), device=device)  # mixture component of every row
+        gen = torch.Generator(device=device)
+        gen.manual_seed(int(host.randint(0, 2 ** 62)))
+        X = torch.zeros((n, self.ld), dtype=torch.float64, device=device)
+        body = X[:, :d]
+        body.normal_(generator=gen)
+        body.mul_(10.0 / math.sqrt(d))
+        Bs = torch.as_tensor(self.B_star, device=device)
+        body.add_((1.5 / d) * Bs[comp])
+        prob = torch.softmax(body @ Bs.t(), dim=1)
+        y = torch.multinomial(prob, 1, generator=gen).reshape(-1).to(torch.float64)
         return X.to(dtype) if dtype != torch.float64 else X, y
 
     def partition(self, p: int, device="cpu", dtype=None):

@@ -7,6 +7,9 @@ Reference quirks reproduced unless ``fix_quirks``:
   * result names follow each scheme's (colliding) prefixes (codes/schemes.py).
 Squared-hinge runs (not in the reference) are scored and printed like logistic ones, and every result
 name carries the prefix ``sqhinge_`` so a run in the same data directory keeps the logistic files.
+Softmax runs are scored by cross-entropy and accuracy: the console line carries the accuracy where the
+logistic line has the AUC, ``EvalResult.auc`` (and the ``auc`` result file) hold the accuracy, and the
+result names carry the prefix ``softmax_``.
 """
 from __future__ import annotations
 
@@ -17,20 +20,22 @@ import numpy as np
 import torch
 
 from ..data import io as dio
-from ..models.losses import SQUARED_HINGE, is_classification
-from ..ops.eval import auc_columns, loss_sums, predictions_and_loss
+from ..models.losses import SQUARED_HINGE, is_classification, is_multiclass
+from ..ops.eval import auc_columns, loss_sums, predictions, predictions_and_loss
 from ..utils import report
 from .trainer import TrainResult, Trainer
 
 
 SQHINGE_PREFIX = "sqhinge_"  # result files of squared-hinge runs (next to the logistic names)
+SOFTMAX_PREFIX = "softmax_"
+SOFTMAX_P_ELEMS = 1 << 26  # logits held at once by the softmax evaluation (rounds are chunked to fit)
 
 
 @dataclass
 class EvalResult:
     training_loss: np.ndarray
     testing_loss: np.ndarray
-    auc: np.ndarray
+    auc: np.ndarray  # softmax runs: the test accuracy of every round
     n_train: int
     n_test: int
     files: Optional[Dict[str, str]] = None
@@ -59,8 +64,60 @@ def _train_chunks(trainer: Trainer, parts, prec, dev):
         yield resident[p]
 
 
+def _softmax_sums(X, y, B, classes: int, d_x: int):
+    """(CE sums [R], correct counts [R]) of the rows X, y for the models B [R * classes, ld_x]: logits from
+    the prediction GEMM (ops/eval.predictions), rounds chunked so the logits stay bounded."""
+    n, R = X.shape[0], B.shape[0] // classes
+    ce = torch.zeros(R, dtype=torch.float64)
+    hit = torch.zeros(R, dtype=torch.float64)
+    step = max(1, SOFTMAX_P_ELEMS // max(1, n * classes))
+    yl = y.to(X.device).long()
+    for r0 in range(0, R, step):
+        r1 = min(R, r0 + step)
+        Z = predictions(X, B[r0 * classes: r1 * classes], d_x).double().reshape(n, r1 - r0, classes)
+        zy = Z.gather(2, yl[:, None, None].expand(n, r1 - r0, 1))[:, :, 0]
+        ce[r0:r1] = (torch.logsumexp(Z, dim=2) - zy).sum(0).cpu()
+        hit[r0:r1] = (Z.argmax(dim=2) == yl[:, None]).double().sum(0).cpu()
+    return ce.numpy(), hit.numpy()
+
+
+def _evaluate_softmax(trainer: Trainer, res: TrainResult, log, write: bool) -> EvalResult:
+    cfg, dev, prec = trainer.cfg, trainer.env.device, trainer.prec
+    C, d_x, ld_x = trainer.classes, trainer.d_x, trainer.ld_x
+    R = res.betaset.shape[0]
+    B = torch.from_numpy(np.ascontiguousarray(res.betaset)).to(dev).reshape(R * C, ld_x)
+    parts = eval_partitions(trainer)
+    if cfg.verbose:
+        log(report.total_time_line(res.total_time))
+    tr_sum, n_train = np.zeros(R), 0
+    for X, y in _train_chunks(trainer, parts, prec, dev):
+        s, _ = _softmax_sums(X, y, B, C, d_x)
+        tr_sum += s
+        n_train += X.shape[0]
+    Xt, yt = trainer.source.test(prec, dev)
+    te_sum, hits = _softmax_sums(Xt, yt, B, C, d_x)
+    n_test = Xt.shape[0]
+    training_loss = tr_sum / max(1, n_train)
+    testing_loss = te_sum / max(1, n_test)
+    acc = hits / max(1, n_test)
+    if cfg.verbose:
+        for i in range(R):
+            log(report.softmax_line(i, training_loss[i], testing_loss[i], acc[i], res.timeset[i]))
+    files = None
+    if write:
+        names = {k: SOFTMAX_PREFIX + v for k, v in trainer.scheme.output_names(cfg.fix_quirks).items()}
+        data_dir = getattr(trainer.source, "data_dir", None) or cfg.input_dir
+        files = report.write_results(dio.results_dir(data_dir), names, training_loss, testing_loss, acc,
+                                     res.timeset, res.worker_timeset, cfg.full_precision_outputs)
+    if cfg.verbose:
+        log(">>> Done")
+    return EvalResult(training_loss, testing_loss, acc, n_train, n_test, files)
+
+
 def evaluate(trainer: Trainer, res: TrainResult, log=None, write: bool = True) -> EvalResult:
     log = log or report.log
+    if is_multiclass(trainer.loss):
+        return _evaluate_softmax(trainer, res, log, write)
     cfg = trainer.cfg
     dev = trainer.env.device
     prec = trainer.prec

@@ -50,8 +50,10 @@ from ..codes.schemes import Arrival, Scheme, SchemeError, make_scheme, scheme_ke
 from ..config import RunConfig
 from ..data import io as dio
 from ..data.source import DataSource, FileSource, SyntheticSource
-from ..models.losses import LEAST_SQUARES, LOGISTIC, LOSS_NAMES, UpdateRule, is_classification
+from ..models.losses import (LEAST_SQUARES, LOGISTIC, LOSS_CHOICES, SOFTMAX, UpdateRule, check_classes,
+                             is_classification)
 from ..ops.grad import DenseGradPlan, SharedGradPlan, SparseGradPlan
+from ..ops.softmax import SoftmaxGradPlan
 from ..ops.precision import get_precision
 from ..ops.update import combine_update
 from ..parallel.collector import ArrivalCollector
@@ -171,9 +173,11 @@ class Trainer:
         if cfg.loss == "auto":
             self.loss = LEAST_SQUARES if (cfg.dataset == "kc_house_data" and scheme.has_linear) else LOGISTIC
         else:
-            if cfg.loss not in LOSS_NAMES:
-                raise ValueError(f"unknown loss {cfg.loss!r}: auto or one of {sorted(LOSS_NAMES)}")
-            self.loss = LOSS_NAMES[cfg.loss]
+            if cfg.loss not in LOSS_CHOICES:
+                raise ValueError(f"unknown loss {cfg.loss!r}: auto or one of {sorted(LOSS_CHOICES)}")
+            self.loss = LOSS_CHOICES[cfg.loss]
+        # multi-class softmax: the model is [classes][ld_x] flattened (ops/softmax.py); 1 for every other loss
+        self.classes = check_classes(cfg.classes or 2) if self.loss == SOFTMAX else 1
         self.rule_kind, self.rule_k = scheme.rule()
         self.update = UpdateRule("AGD" if scheme.fixed_agd else cfg.update_rule, cfg.alpha_value, cfg.n_rows,
                                  scheme.grad_scale())
@@ -231,30 +235,40 @@ class Trainer:
         self.prec = get_precision(cfg.precision)
         if source is None:
             if cfg.data == "synthetic":
-                source = SyntheticSource(cfg.n_rows, cfg.n_cols, sch.n_partition_files, cfg.data_seed)
+                source = SyntheticSource(cfg.n_rows, cfg.n_cols, sch.n_partition_files, cfg.data_seed,
+                                         classes=self.classes if self.loss == SOFTMAX else None)
             else:
                 data_dir = dio.dataset_dir(cfg.input_dir, cfg.is_real, cfg.dataset, cfg.n_rows, cfg.n_cols)
                 data_dir = data_dir + sch.data_subdir()
                 source = FileSource(data_dir, cfg.is_real, sch.rows_per_partition, cfg.n_cols)
         self.source = source
-        self.d = cfg.n_cols
-        self.ld = self.prec.ld(self.d)
+        # d_x / ld_x: the data's columns and row stride; d / ld: everything model-sized (beta, messages,
+        # history).  They differ only for softmax, whose model is the flattened [classes][ld_x].
+        self.d_x = cfg.n_cols
+        self.ld_x = self.prec.ld(self.d_x)
+        self.d, self.ld = self.d_x, self.ld_x
+        if self.loss == SOFTMAX:
+            self.d = self.ld = self.classes * self.ld_x
+            SoftmaxGradPlan.check_supported(self.prec, self.classes, source.is_sparse)  # before any load
         dev = self.env.device
         needed = sorted({p for m in self.local_msgs for p, _ in m.segments})
         if not source.is_sparse and self.env.gpu:
-            self._check_hbm(len(needed) * sch.rows_per_partition * self.ld * self.prec.storage_bytes)
+            self._check_hbm(len(needed) * sch.rows_per_partition * self.ld_x * self.prec.storage_bytes)
         t0 = time.perf_counter()
         parts = {p: source.partition(p, self.prec, dev) for p in needed}
         self.load_seconds = time.perf_counter() - t0
         segs = [m.segments for m in self.local_msgs]
 
         def make_plan(messages):
+            if self.loss == SOFTMAX:  # shares the distinct partitions by itself: --share-partitions changes nothing
+                return SoftmaxGradPlan(messages, parts, self.prec, self.classes, self.d_x)
             if source.is_sparse:
                 return SparseGradPlan(messages, parts, self.prec, self.loss, self.d, device=dev)
             kw = {"target_tasks": cfg.tasks} if cfg.tasks else {}
             return DenseGradPlan(messages, parts, self.prec, self.loss, self.d, **kw)
 
-        if cfg.share_partitions and SharedGradPlan.worthwhile(segs, lambda p: parts[p][0].shape[0]):
+        share = cfg.share_partitions and self.loss != SOFTMAX
+        if share and SharedGradPlan.worthwhile(segs, lambda p: parts[p][0].shape[0]):
             self.plan = SharedGradPlan(segs, make_plan)
         else:
             self.plan = make_plan(segs)
@@ -357,7 +371,7 @@ class Trainer:
         counts = collections.Counter(p for m in self.local_msgs for p, _ in m.segments)
         if not counts or max(counts.values()) < 2:
             return "none"
-        if isinstance(plan, (SharedGradPlan, SparseGradPlan)):
+        if isinstance(plan, (SharedGradPlan, SparseGradPlan, SoftmaxGradPlan)):
             return "encoded"
         return "separate"
 
@@ -365,12 +379,17 @@ class Trainer:
     def _init_beta(self):
         """beta_0: randn (naive/replication/approx) or zeros (ref §2.2 'Per-scheme beta init')."""
         d = self.d
+        nb = self.classes * self.d_x  # softmax: classes * d_x values, scattered into [classes][:d_x] below
         if self.scheme.init_zero:
-            b0 = np.zeros(d)
+            b0 = np.zeros(nb)
         elif self.cfg.seed is not None:
-            b0 = np.random.RandomState(self.cfg.seed + 1).randn(d)
+            b0 = np.random.RandomState(self.cfg.seed + 1).randn(nb)
         else:
-            b0 = np.random.randn(d)
+            b0 = np.random.randn(nb)
+        if self.loss == SOFTMAX:  # the padding columns of every class block stay zero
+            full = np.zeros((self.classes, self.ld_x))
+            full[:, : self.d_x] = b0.reshape(self.classes, self.d_x)
+            b0 = full.ravel()
         self.beta.zero_()
         self.beta[:d] = torch.from_numpy(b0).to(self.beta.device)
         self.u.zero_()

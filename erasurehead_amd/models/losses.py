@@ -14,6 +14,14 @@ of the device path so the HIP kernels can be checked against them:
   MSE                        mean (y - p)^2                                  ref src/util.py:139-141
   squared-hinge loss         mean max(0, 1 - y * p)^2
   AUC                        area under ROC of scores p vs labels in {-1,1}  ref src/naive.py:196-197
+
+Multi-class softmax regression (not in the reference): labels are class indices 0..C-1, the model is
+B [C, d] and travels flattened class-major (on the device [C][ld_x], padding columns zero):
+  logits / probabilities     z_c = x . B_c,  p = softmax(z)  (max_c z_c subtracted before exp)
+  worker gradient            G_c = sum_rows coef (p_c - [y = c]) x    (the scale of logistic_grad: C = 2 with
+                             B_0 = 0, B_1 = beta gives G_1 = logistic_grad(X, 2y - 1, beta), G_0 = -G_1)
+  cross-entropy              CE = logsumexp(z) - z_y  (never -log p_y)
+  step size                  the CE Hessian is bounded by XtX / 2 (logistic: XtX / 4): lr 5 where logistic uses 10
 """
 from __future__ import annotations
 
@@ -25,7 +33,22 @@ import numpy as np
 LOGISTIC = 0
 LEAST_SQUARES = 1
 SQUARED_HINGE = 2
+SOFTMAX = 3
 LOSS_NAMES = {"logistic": LOGISTIC, "least_squares": LEAST_SQUARES, "squared_hinge": SQUARED_HINGE}
+# every loss a run can name (--loss): the per-row scalar losses above plus the multi-class model
+LOSS_CHOICES = {**LOSS_NAMES, "softmax": SOFTMAX}
+MIN_CLASSES, MAX_CLASSES = 2, 8  # csrc/kernels/launchers.h kSoftmaxMaxClasses
+
+
+def is_multiclass(kind: int) -> bool:
+    """Losses over class-index labels with a [C, d] model: scored by accuracy."""
+    return kind == SOFTMAX
+
+
+def check_classes(classes: int) -> int:
+    if not MIN_CLASSES <= int(classes) <= MAX_CLASSES:
+        raise ValueError(f"classes must be in {MIN_CLASSES}..{MAX_CLASSES}, got {classes}")
+    return int(classes)
 
 
 def is_classification(kind: int) -> bool:
@@ -66,10 +89,63 @@ def squared_hinge_grad(X, y: np.ndarray, beta: np.ndarray, coef=None) -> np.ndar
     return np.asarray(X.T.dot(r)).ravel()
 
 
+def _logits(X, B: np.ndarray) -> np.ndarray:
+    return np.asarray(X.dot(np.asarray(B, dtype=np.float64).T))
+
+
+def softmax_grad(X, y: np.ndarray, B: np.ndarray, coef=None) -> np.ndarray:
+    """[C, d]: G_c = X^T (coef * (softmax(X B^T)_c - [y = c])); y holds class indices."""
+    Z = _logits(X, B)
+    E = np.exp(Z - Z.max(axis=1, keepdims=True))
+    R = E / E.sum(axis=1, keepdims=True)
+    R[np.arange(len(y)), np.asarray(y).astype(np.int64)] -= 1.0
+    if coef is not None:
+        R = R * coef
+    return np.asarray(X.T.dot(R)).T
+
+
+def softmax_ce(y: np.ndarray, Z: np.ndarray) -> np.ndarray:
+    """Per-row cross-entropy logsumexp(z) - z_y from logits Z [n, C]."""
+    Z = np.asarray(Z, dtype=np.float64)
+    m = Z.max(axis=1)
+    lse = m + np.log(np.exp(Z - m[:, None]).sum(axis=1))
+    return lse - Z[np.arange(len(y)), np.asarray(y).astype(np.int64)]
+
+
+def softmax_loss(y: np.ndarray, Z: np.ndarray, n: Optional[int] = None) -> float:
+    """(1/n) sum CE over logits Z [n, C]."""
+    return float(softmax_ce(y, Z).sum() / (len(y) if n is None else n))
+
+
+def accuracy(y: np.ndarray, Z: np.ndarray) -> float:
+    """Share of rows whose largest logit (first on ties) is their label."""
+    return float(np.mean(np.argmax(np.asarray(Z), axis=1) == np.asarray(y).astype(np.int64)))
+
+
+def softmax_unpack(betaset: np.ndarray, classes: int, d_x: int) -> np.ndarray:
+    """[R, C * ld_x] flattened class-major models (as the engine stores them) -> [R, C, d_x]."""
+    b = np.asarray(betaset)
+    b = b.reshape(1, -1) if b.ndim == 1 else b
+    if b.shape[1] % classes or b.shape[1] // classes < d_x:
+        raise ValueError(f"model length {b.shape[1]} is not {classes} class blocks of >= {d_x} columns")
+    return b.reshape(b.shape[0], classes, b.shape[1] // classes)[:, :, :d_x]
+
+
+def softmax_pack(B: np.ndarray, ld_x: int) -> np.ndarray:
+    """[C, d_x] -> flattened class-major [C * ld_x] with zero padding columns."""
+    B = np.asarray(B, dtype=np.float64)
+    out = np.zeros((B.shape[0], ld_x))
+    out[:, : B.shape[1]] = B
+    return out.ravel()
+
+
 _GRADS = {LOGISTIC: logistic_grad, LEAST_SQUARES: least_squares_grad, SQUARED_HINGE: squared_hinge_grad}
 
 
 def worker_grad(kind: int, X, y, beta, coef=None) -> np.ndarray:
+    if kind == SOFTMAX:  # beta: the flattened [C, X.shape[1]] model; returns the gradient flattened alike
+        d = X.shape[1]
+        return softmax_grad(X, y, np.asarray(beta).reshape(np.size(beta) // d, d), coef).ravel()
     if kind not in _GRADS:
         raise ValueError(f"unknown loss kind {kind}")
     return _GRADS[kind](X, y, beta, coef)

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from .._ext import native
-from ..models.losses import LEAST_SQUARES, LOGISTIC, SQUARED_HINGE
+from ..models.losses import LEAST_SQUARES, LOGISTIC, SOFTMAX, SQUARED_HINGE
 from .precision import Precision
 
 _SEG = struct.Struct("<QQdq")  # csrc Segment {const void* X; const void* y; double coef; long long nrows}
@@ -391,6 +391,12 @@ def replica_dispatch_order(keys: Sequence[Tuple[int, int]], stride: int = 0) -> 
     return order
 
 
+def _reject_softmax(loss: int) -> None:
+    """The scalar-residual plans cannot run the multi-class model (ops/softmax.py SoftmaxGradPlan does)."""
+    if loss == SOFTMAX:
+        raise ValueError("softmax is not a per-row scalar loss: use SoftmaxGradPlan (dense partitions only)")
+
+
 def _residual_torch(kind: int, z, y, coef):
     if kind == LOGISTIC:
         return -(coef * y) * torch.sigmoid(-(y * z))
@@ -412,6 +418,7 @@ class DenseGradPlan:
                  partitions: Dict[int, Tuple[torch.Tensor, torch.Tensor]], prec: Precision, loss: int, d: int,
                  target_tasks: Optional[int] = None, choice: Optional[KernelChoice] = None):
         """choice: the kernel to launch (tests / sweeps); default: :func:`choose_kernel`'s measured pick."""
+        _reject_softmax(loss)
         self.prec = prec
         self.loss = loss
         self.d = d
@@ -661,6 +668,7 @@ class SparseGradPlan:
                  prec: Precision, loss: int, d: int, device="cpu", use_ell="auto"):
         import scipy.sparse as sps
 
+        _reject_softmax(loss)
         if prec.name == "bf16":
             raise ValueError("sparse data uses fp64 or fp32 values (bf16 has no benefit for one-hot data)")
         self.prec, self.loss, self.d = prec, loss, d

@@ -5,6 +5,7 @@
   Total Time Elapsed: %.3f
   Iteration %d: Train Loss = %5.3f, Test Loss = %5.3f, AUC = %5.3f, Total time taken =%5.3f   (logistic, squared hinge)
   Iteration %d: Train Loss = %.6f, Test Loss = %.6f, Total time taken =%5.3f                  (least squares)
+  Iteration %d: Train Loss = %5.3f, Test Loss = %5.3f, Accuracy = %5.3f, Total time taken =%5.3f   (softmax)
   >>> Done
 ref src/naive.py:86,93,156,198,209 and :407; files via ref src/util.py:26-36.
 """
@@ -34,6 +35,11 @@ def total_time_line(t: float) -> str:
 def logistic_line(i: int, train: float, test: float, auc: float, t: float) -> str:
     return "Iteration %d: Train Loss = %5.3f, Test Loss = %5.3f, AUC = %5.3f, Total time taken =%5.3f" % (
         i, train, test, auc, t)
+
+
+def softmax_line(i: int, train: float, test: float, acc: float, t: float) -> str:
+    return "Iteration %d: Train Loss = %5.3f, Test Loss = %5.3f, Accuracy = %5.3f, Total time taken =%5.3f" % (
+        i, train, test, acc, t)
 
 
 def linear_line(i: int, train: float, test: float, t: float) -> str:

@@ -1,0 +1,38 @@
+"""One rank of a multi-process softmax run (torchrun from tests/test_softmax_cpu.py / test_softmax_gpu.py).
+
+python -m torch.distributed.run --nproc-per-node N tests/mp_softmax_run.py
+  EH_SOFTMAX_OUT     the .npz rank 0 writes: betaset, beta0, the per-round arrival lists, the transport's name
+  EH_SOFTMAX_DEVICE  cpu (gloo) or cuda (ranks sharing one GPU: IPC mailboxes, integrity tags on)
+Builds the seeded AGC case of tests/test_softmax_cpu.py::make (uneven groups, C = 3, d_x = 33, AGD).
+"""
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
+
+import numpy as np  # noqa: E402
+
+
+def main():
+    from erasurehead_amd.engine import Trainer
+    from erasurehead_amd.parallel.dist import init_distributed
+    from test_softmax_cpu import CASES, make
+
+    env = init_distributed(os.environ.get("EH_SOFTMAX_DEVICE", "cuda"))
+    cfg, src, sch, parts = make(CASES["agc_uneven"], "AGD")
+    cfg.integrity = True
+    tr = Trainer(cfg, env, src, scheme=sch)
+    res = tr.run()
+    if env.is_master:
+        arr = np.array([[(w, p, 0.0) for (w, p, _) in a] for a in res.arrivals], dtype=object)
+        np.savez(os.environ["EH_SOFTMAX_OUT"], betaset=res.betaset, beta0=tr.beta0, arrivals=arr,
+                 transport=np.array(tr.transport))
+    env.barrier()
+    tr.close()
+    env.shutdown()
+
+
+if __name__ == "__main__":
+    main()

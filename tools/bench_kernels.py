@@ -7,6 +7,7 @@
 * ``--only sweep``: d in {256, 1000, 2048, 4096} x n in {1e5, 1e6, 4e6} x fp64/fp32 against the
   device-copy ceiling, distinct-row and replica-bundle layouts; ``--loss a,b,...`` times each named
   loss on the same data in the same process, in the order given (repeat names to alternate);
+  ``softmax`` among them times the one-pass multi-class kernel for every ``--classes C,...``;
 * sparse one-hot gradients on covtype / kc_house / amazon-shaped data (the reference's real
   datasets, synthetic stand-ins of the same shape): the ELL path against the generic
   sorted-COO path.
@@ -133,7 +134,7 @@ def scale_cases(out):
 
 
 def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_000), precs=("fp64", "fp32"),
-                losses=("logistic",)):
+                losses=("logistic",), classes=(2,)):
     """Shape sweep of the dense gradient against the device-copy ceiling (round-2 verdict item 6).
 
     For every (precision, d, n): n rows in 8 partitions, two message layouts -- ``naive`` (one
@@ -142,11 +143,13 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
     ceiling is a device-to-device copy of one partition (read + write bytes / time); ``frac`` is the
     kernel's distinct-X read rate over it.  Every loss of ``losses`` runs on the same tensors, one after
     the other (the kernels are branch-free in the data, so beta's scale does not enter the time).
+    ``softmax`` runs SoftmaxGradPlan on the same X with labels randint(0, C), once per C of ``classes``
+    (rows of at most 1024 columns, fp64 / fp32).
     """
     import torch
 
     from erasurehead_amd.models.losses import LOSS_NAMES
-    from erasurehead_amd.ops import DenseGradPlan, get_precision
+    from erasurehead_amd.ops import DenseGradPlan, SoftmaxGradPlan, get_precision
 
     layouts = {"naive": [[p] for p in range(8)], "agc": [[0, 1, 2]] * 3 + [[3, 4, 5]] * 3 + [[6, 7]] * 2}
     for prec_name in precs:
@@ -167,6 +170,23 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
                 beta = torch.randn(prec.ld(d), device="cuda", dtype=prec.acc) * 0.01
                 for lay, msgs in layouts.items():
                     for loss in losses:
+                        if loss == "softmax":
+                            for C in classes:
+                                sm = {p: (X, torch.randint(0, C, (rpp,), device="cuda").to(prec.acc))
+                                      for p, (X, _) in parts.items()}
+                                plan = SoftmaxGradPlan([[(p, 1.0) for p in m] for m in msgs], sm, prec, C, d)
+                                bC = torch.randn(plan.ld, device="cuda", dtype=prec.acc) * 0.01
+                                G = plan.out_buffer()[0]
+                                ms = _time(lambda: plan.run(bC, G), reps=20)
+                                distinct = 8 * nbytes / 1e12  # TB
+                                r = {"kernel": "grad_softmax_sweep", "precision": prec_name, "d": d, "n": n,
+                                     "layout": lay, "loss": loss, "classes": C, "tasks": plan.ntasks, "ms": ms,
+                                     "distinct_TBps": distinct / ms * 1e3, "copy_TBps": ceiling,
+                                     "frac": distinct / ms * 1e3 / ceiling}
+                                out.append(r)
+                                print(json.dumps(r), flush=True)
+                                del plan, G, sm
+                            continue
                         plan = DenseGradPlan([[(p, 1.0) for p in m] for m in msgs], parts, prec, LOSS_NAMES[loss], d)
                         G = plan.out_buffer()[0]
                         ms = _time(lambda: plan.run(beta, G), reps=20)
@@ -317,7 +337,9 @@ def main():
     ap.add_argument("--ns", default="1e5,1e6,4e6", help="--only sweep: row counts")
     ap.add_argument("--precs", default="fp64,fp32", help="--only sweep: precisions")
     ap.add_argument("--loss", default="logistic",
-                    help="--only sweep: losses timed on the same data, in order (logistic, least_squares, squared_hinge)")
+                    help="--only sweep: losses timed on the same data, in order (logistic, least_squares, squared_hinge, "
+                         "softmax)")
+    ap.add_argument("--classes", default="2", help="--only sweep --loss softmax: class counts, e.g. 2,4,7,8")
     ap.add_argument("--sparse-shapes", default="covtype,kc_house_data,amazon-dataset", help="--only sparse: datasets")
     ap.add_argument("--ell-only", action="store_true", help="--only sparse: skip the CSR row pass")
     ap.add_argument("--sparse-layouts", default=None, help="--only sparse: naive,s1_replicas,frc_s1 (default: all)")
@@ -342,11 +364,11 @@ def main():
         SparseGradPlan.WG_SPANS = not a.no_wg_spans
         SparseGradPlan.WG_TILES = a.wg_tiles or SparseGradPlan.WG_TILES
         SparseGradPlan.WG_SLOTS = a.wg_slots or SparseGradPlan.WG_SLOTS
-    from erasurehead_amd.models.losses import LOSS_NAMES
+    from erasurehead_amd.models.losses import LOSS_CHOICES
 
     losses = tuple(a.loss.split(","))
-    if any(x not in LOSS_NAMES for x in losses):
-        ap.error(f"--loss: names from {sorted(LOSS_NAMES)}")
+    if any(x not in LOSS_CHOICES for x in losses):
+        ap.error(f"--loss: names from {sorted(LOSS_CHOICES)}")
     out = []
     if a.only in (None, "dense"):
         dense_cases(out)
@@ -356,7 +378,7 @@ def main():
         eval_cases(out)
     if a.only == "sweep":
         sweep_cases(out, ds=tuple(int(x) for x in a.ds.split(",")), ns=tuple(int(float(x)) for x in a.ns.split(",")),
-                    precs=tuple(a.precs.split(",")), losses=losses)
+                    precs=tuple(a.precs.split(",")), losses=losses, classes=tuple(int(c) for c in a.classes.split(",")))
     if a.only == "choices":
         if a.shapes:
             choice_cases(out, [(p, int(d), int(float(n))) for p, d, n in (x.split(":") for x in a.shapes.split(","))],
