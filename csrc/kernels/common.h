@@ -271,6 +271,20 @@ inline hipError_t dispatch_loss(int loss, F&& f) {
   }
 }
 
+// Runtime storage code (launchers.h dtype) -> compile-time (storage T, accumulator A): 0 double / double,
+// 1 float / float, 2 bf16_t / float.  f is called with a StorageTag and returns a hipError_t; an unknown
+// code launches nothing.
+template <typename T_, typename A_> struct StorageTag { using T = T_; using A = A_; };
+template <typename F>
+inline hipError_t dispatch_storage(int dtype, F&& f) {
+  switch (dtype) {
+    case 0: return f(StorageTag<double, double>{});
+    case 1: return f(StorageTag<float, float>{});
+    case 2: return f(StorageTag<bf16_t, float>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+
 template <typename A>
 __device__ __forceinline__ A sigmoid_neg(A t) {
   // 1 / (exp(t) + 1), overflow-free in both directions.

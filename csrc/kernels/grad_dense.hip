@@ -14,26 +14,21 @@
 // register slice of g.  ROWS rows are loaded per wave iteration as raw 16-byte tiles (every
 // load issues before the first conversion waits), so the reduction latency of one row
 // overlaps the loads of the others; the rows-in-flight count is tuned per storage type.  At the end each workgroup
-// folds its 4 waves through LDS and writes one fp64/fp32 slab row; a second tiny
-// kernel sums the slab rows of each output message in a fixed order (bitwise
-// reproducible, no float atomics).
+// folds its 4 waves through LDS and writes one fp64/fp32 slab row; the slab reduction
+// (slab_reduce.hip, launched from here through slab_reduce.h) then sums the slab rows of each
+// output message in a fixed order (bitwise reproducible, no float atomics).
 //
 // The "task" table lets one launch serve every logical worker hosted on this GPU
 // (e.g. all 8 FRC/AGC workers at N=1): task -> (output message slot, segment,
 // row range); segment -> (partition base pointer, labels, encoding coefficient).
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <map>
-#include <mutex>
-#include <string>
-#include <tuple>
 #include <type_traits>
 
 #include "common.h"
 #include "grad_dense.h"
 #include "launchers.h"
 #include "lds_dma.h"
+#include "slab_reduce.h"
 
 namespace eh {
 
@@ -1033,361 +1028,6 @@ grad_dense_wide(const Segment* __restrict__ segs, const Task* __restrict__ tasks
   }
 }
 
-// Slab reduction, two fixed-order stages (bitwise reproducible, no atomics):
-//   stage 1: block (64-column chunk, slot, split) — 4 waves stride over the split's tasks,
-//            lane = column, then fold the waves in LDS -> part[slot][split][c]
-//   stage 2: G[slot][c] = sum over splits of part[slot][split][c]
-// 16 splits x 16 column chunks x slots gives thousands of workgroups for what used to be
-// a 32-workgroup serial loop (70 us -> a few us at 2048 tasks x 1000 columns).
-constexpr int kSplits = 16;
-// Slab reduction form of the non-update paths (set_slab_reduce_mode, for same-box A/B by
-// tools/bench_kernels.py --only reduce): 1 = one fused launch for plain reductions and puts
-// (slab_reduce_fused[_put]); 2 = fused plain reductions, puts as stage 1 + the put kernel;
-// 0 = the two stages everywhere.
-static int g_slab_mode = 1;
-// Timeline probe of grad_dense_multi (set_grad_stamps; nullptr = off, every production launch).
-static long long* g_stamps = nullptr;
-
-template <typename A>
-__global__ void __launch_bounds__(256)
-slab_reduce_partial(const A* __restrict__ slab, const int* __restrict__ slot_task_begin,
-                    A* __restrict__ part, int ld, const int* __restrict__ gate) {
-  __shared__ A red[4][kWave];
-  if (gate_closed(gate)) return;
-  const int slot = blockIdx.y, split = blockIdx.z;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int c = blockIdx.x * kWave + lane;
-  const int tb = slot_task_begin[slot], te = slot_task_begin[slot + 1];
-  const int per = (te - tb + kSplits - 1) / kSplits;
-  const int t0 = tb + split * per;
-  const int t1 = min(te, t0 + per);
-  A s = A(0);
-  if (c < ld)
-    for (int t = t0 + wid; t < t1; t += 4) s += slab[static_cast<long long>(t) * ld + c];
-  red[wid][lane] = s;
-  __syncthreads();
-  if (wid == 0 && c < ld)
-    part[(static_cast<long long>(slot) * kSplits + split) * ld + c] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
-}
-
-template <typename A>
-__global__ void __launch_bounds__(256)
-slab_reduce_final(const A* __restrict__ part, A* __restrict__ G, int ld, const int* __restrict__ gate) {
-  const int slot = blockIdx.y;
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= ld || gate_closed(gate)) return;
-  A s = A(0);
-#pragma unroll
-  for (int k = 0; k < kSplits; ++k) s += part[(static_cast<long long>(slot) * kSplits + k) * ld + c];
-  G[static_cast<long long>(slot) * ld + c] = s;
-}
-
-// Both stages in ONE launch, bitwise the same sums: a 1024-thread block per (64-column chunk, slot),
-// wave k = split k.  Lane c of wave k keeps the four interleaved sums stage 1's waves kept (rows
-// t0 + w, t0 + w + 4, ... of its split, each in row order; eight rows loaded per step), folds them
-// as (s0 + s1) + (s2 + s3), and wave 0 adds the 16 splits in order from A(0) like stage 2.  One launch
-// and no partial buffer in HBM instead of two back-to-back launches (5.7 + 4.7 us at the 8-GPU rank
-// shape, profiles/round4/prof_shape8).
-template <typename A>
-__device__ __forceinline__ A fused_split_sum(const A* __restrict__ slab, int t0, int t1, int ld, int c) {
-  A acc[4] = {A(0), A(0), A(0), A(0)};
-  int t = t0;
-  for (; t + 8 <= t1; t += 8) {
-    A v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = slab[static_cast<long long>(t + j) * ld + c];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j & 3] += v[j];  // accumulator (t - t0) % 4, rows in order
-  }
-  for (; t < t1; ++t) acc[(t - t0) & 3] += slab[static_cast<long long>(t) * ld + c];
-  return (acc[0] + acc[1]) + (acc[2] + acc[3]);
-}
-
-template <typename A>
-__device__ __forceinline__ A fused_slab_sum(const A* __restrict__ slab, const int* __restrict__ slot_task_begin,
-                                            A (*red)[kWave], int slot, int ld, int c) {
-  const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
-  const int tb = slot_task_begin[slot], te = slot_task_begin[slot + 1];
-  const int per = (te - tb + kSplits - 1) / kSplits;
-  const int t0 = tb + k * per;
-  const int t1 = min(te, t0 + per);
-  red[k][lane] = c < ld && t0 < t1 ? fused_split_sum(slab, t0, t1, ld, c) : A(0);
-  __syncthreads();
-  A s = A(0);
-  if (k == 0)
-#pragma unroll
-    for (int q = 0; q < kSplits; ++q) s += red[q][lane];
-  return s;  // meaningful in wave 0
-}
-
-template <typename A>
-__global__ void __launch_bounds__(1024)
-slab_reduce_fused(const A* __restrict__ slab, const int* __restrict__ slot_task_begin, A* __restrict__ G, int ld,
-                  const int* __restrict__ gate) {
-  __shared__ A red[kSplits][kWave];
-  if (gate_closed(gate)) return;
-  const int slot = blockIdx.y, c = blockIdx.x * kWave + (threadIdx.x & 63);
-  const A s = fused_slab_sum(slab, slot_task_begin, red, slot, ld, c);
-  if ((threadIdx.x >> 6) == 0 && c < ld) G[static_cast<long long>(slot) * ld + c] = s;
-}
-
-// The same with the worker's message put (slab_reduce_final_put's protocol: every block releases its
-// columns and counts itself done; the last block writes the tags, releases them and stores the flag).
-template <typename A>
-__global__ void __launch_bounds__(1024)
-slab_reduce_fused_put(const A* __restrict__ slab, const int* __restrict__ slot_task_begin, A* __restrict__ G, int ld,
-                      PutDesc put) {
-  __shared__ A red[kSplits][kWave];
-  __shared__ int s_last, s_live;
-  const int slot = blockIdx.y, c = blockIdx.x * kWave + (threadIdx.x & 63);
-  const bool w0 = (threadIdx.x >> 6) == 0;
-  if (gate_closed(put.gate)) {  // a skipped stale round (launch-uniform): decide the next one's gate
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) put_decide_next_gate(put);
-    return;
-  }
-  if (threadIdx.x == 0) s_live = !(put.abort && __hip_atomic_load(put.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-  const A s = fused_slab_sum(slab, slot_task_begin, red, slot, ld, c);  // (its barrier publishes s_live)
-  const bool live = s_live;
-  if (w0 && c < ld) {
-    const long long o = static_cast<long long>(slot) * ld + c;
-    G[o] = s;
-    if (live) static_cast<A*>(put.dst)[o] = s;
-  }
-  if (!live) return;  // block-uniform
-  if (put.tag && w0) {
-    const unsigned long long ws = wave_sum_u64(c < ld ? tag_term(elem_bits(s), c) : 0ull);
-    if (threadIdx.x == 0 && ws) atomicAdd(put.csum + slot, ws);
-  }
-  block_release_system(put.strict);  // this block's mailbox columns (and checksum adds) are out before its count
-  if (threadIdx.x == 0) {
-    const unsigned int total = gridDim.x * gridDim.y;
-    const unsigned int prev = count_block_done(put.counter, put.strict);
-    s_last = prev == total - 1;
-    if (s_last) __hip_atomic_store(put.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (!s_last) return;  // block-uniform
-  if (put.tag) {
-    for (int r = threadIdx.x; r < static_cast<int>(gridDim.y); r += blockDim.x) {
-      const unsigned long long sum = atomicExch(put.csum + r, 0ull);
-      put.tag[r] = MsgTag{static_cast<unsigned int>(put.value), put.rank, sum};
-    }
-    if (put.corrupt && threadIdx.x == 0) static_cast<unsigned char*>(put.dst)[1] ^= 0x10;  // test hook
-  }
-  if (threadIdx.x == 0) put_stamp(put);
-  block_release_system(put.strict);  // the tags (and the landing stamp) before the flag
-  if (threadIdx.x == 0) {
-    publish_u64(put.flag, put.value, put.strict);
-    put_decide_next_gate(put);
-  }
-}
-
-// Stage 2 fused with the worker's message put (transport.hip's put + signal protocol): every
-// block also stores its sums straight into the receiver's mailbox rows (put.dst, the same
-// [slot][ld] layout as G), releases them at system scope (block_release_system) and counts
-// itself done; the last block resets the counter and stores the flag behind its own release.  Saves the separate put_signal launch on
-// every worker round's critical path.  No early return: every thread reaches the barrier.
-// Tagged puts (put.tag != nullptr, integrity.h): every block also adds its columns' checksum
-// terms of its slot's row into the sender scratch put.csum[slot]; the last block turns the sums
-// into the receiver's tags before the flag.  put.abort set: the pump gave up, G is still
-// written (the local copy) but nothing is put or announced.
-template <typename A>
-__global__ void __launch_bounds__(256)
-slab_reduce_final_put(const A* __restrict__ part, A* __restrict__ G, int ld, PutDesc put) {
-  __shared__ unsigned long long scratch[4];
-  __shared__ int s_last, s_live;
-  const int slot = blockIdx.y;
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (gate_closed(put.gate)) {  // a skipped stale round (launch-uniform): decide the next one's gate
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) put_decide_next_gate(put);
-    return;
-  }
-  if (threadIdx.x == 0)  // one read, shared: every wave of the block takes the same branch
-    s_live = !(put.abort && __hip_atomic_load(put.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-  __syncthreads();
-  const bool live = s_live;
-  unsigned long long term = 0;
-  if (c < ld) {
-    A s = A(0);
-#pragma unroll
-    for (int k = 0; k < kSplits; ++k) s += part[(static_cast<long long>(slot) * kSplits + k) * ld + c];
-    const long long o = static_cast<long long>(slot) * ld + c;
-    G[o] = s;
-    if (live) static_cast<A*>(put.dst)[o] = s;
-    term = tag_term(elem_bits(s), c);
-  }
-  if (!live) return;  // block-uniform
-  if (put.tag) {
-    const unsigned long long bs = block_sum_u64(term, scratch);
-    if (threadIdx.x == 0 && bs) atomicAdd(put.csum + slot, bs);
-  }
-  block_release_system(put.strict);  // this block's mailbox columns (and checksum adds) are out before its count
-  if (threadIdx.x == 0) {
-    const unsigned int total = gridDim.x * gridDim.y;
-    const unsigned int prev = count_block_done(put.counter, put.strict);
-    s_last = prev == total - 1;
-    if (s_last) __hip_atomic_store(put.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (!s_last) return;  // block-uniform
-  if (put.tag) {
-    for (int r = threadIdx.x; r < static_cast<int>(gridDim.y); r += blockDim.x) {
-      const unsigned long long sum = atomicExch(put.csum + r, 0ull);
-      put.tag[r] = MsgTag{static_cast<unsigned int>(put.value), put.rank, sum};
-    }
-    if (put.corrupt && threadIdx.x == 0) static_cast<unsigned char*>(put.dst)[1] ^= 0x10;  // test hook
-  }
-  if (threadIdx.x == 0) put_stamp(put);
-  block_release_system(put.strict);  // the tags (and the landing stamp) before the flag
-  if (threadIdx.x == 0) {
-    publish_u64(put.flag, put.value, put.strict);
-    put_decide_next_gate(put);
-  }
-}
-
-// Stage 2 + put of a SMALL message set (nslots * ld <= kPutOneElems: the 8-GPU rank's 3 x 1000) in
-// ONE 1024-thread block: no cross-block counter and no second release -- the block sums its
-// elements two at a time (32 split loads in flight per thread), keeps the tag checksums in LDS
-// (integer adds, order-free), writes the tags, releases once and stores the flag.  The multi-block
-// form pays a device-scope atomic round trip and the last block's own release on top.
-constexpr int kPutOneElems = 4096, kPutOneSlots = 16;
-
-template <typename A>
-__global__ void __launch_bounds__(1024)
-slab_reduce_final_put1(const A* __restrict__ part, A* __restrict__ G, int ld, int nslots, PutDesc put) {
-  __shared__ unsigned long long tsum[kPutOneSlots];
-  __shared__ int s_live;
-  const int tid = threadIdx.x;
-  if (gate_closed(put.gate)) {  // a skipped stale round (launch-uniform)
-    if (tid == 0) put_decide_next_gate(put);
-    return;
-  }
-  if (tid < kPutOneSlots) tsum[tid] = 0;
-  if (tid == 0) s_live = !(put.abort && __hip_atomic_load(put.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-  __syncthreads();
-  const bool live = s_live;
-  const int n = nslots * ld;
-  for (int e0 = tid; e0 < n; e0 += 2 * static_cast<int>(blockDim.x)) {
-    const int e1 = e0 + static_cast<int>(blockDim.x);
-    const int q0 = e0 / ld, c0 = e0 - q0 * ld;
-    const bool two = e1 < n;
-    const int q1 = two ? e1 / ld : q0, c1 = two ? e1 - q1 * ld : c0;
-    A v0[kSplits], v1[kSplits];
-#pragma unroll
-    for (int k = 0; k < kSplits; ++k) {
-      v0[k] = part[(static_cast<long long>(q0) * kSplits + k) * ld + c0];
-      v1[k] = part[(static_cast<long long>(q1) * kSplits + k) * ld + c1];
-    }
-    A s0 = A(0), s1 = A(0);
-#pragma unroll
-    for (int k = 0; k < kSplits; ++k) {  // slab_reduce_final's order
-      s0 += v0[k];
-      s1 += v1[k];
-    }
-    G[e0] = s0;
-    if (live) static_cast<A*>(put.dst)[e0] = s0;
-    if (put.tag) atomicAdd(&tsum[q0], tag_term(elem_bits(s0), c0));
-    if (two) {
-      G[e1] = s1;
-      if (live) static_cast<A*>(put.dst)[e1] = s1;
-      if (put.tag) atomicAdd(&tsum[q1], tag_term(elem_bits(s1), c1));
-    }
-  }
-  if (!live) return;  // block-uniform
-  if (put.tag) {
-    __syncthreads();
-    if (tid < nslots) put.tag[tid] = MsgTag{static_cast<unsigned int>(put.value), put.rank, tsum[tid]};
-    if (put.corrupt && tid == 0) static_cast<unsigned char*>(put.dst)[1] ^= 0x10;  // test hook
-  }
-  if (tid == 0) put_stamp(put);
-  block_release_system(put.strict);  // the rows, tags (and the landing stamp) before the flag
-  if (tid == 0) {
-    publish_u64(put.flag, put.value, put.strict);
-    put_decide_next_gate(put);
-  }
-}
-
-// Stage 2 + the master's combine and update of a device-driven local round in one launch
-// (MasterPump::run_local; update.hip combine_update's arithmetic).  One block per 64-column chunk:
-// its waves sum the chunk's splits for every slot (slab_reduce_final's order; G rows written, sums
-// kept in LDS), then wave 0 combines the decoded messages in message order and updates beta / u /
-// history / the next worker beta for those columns.  Replaces slab_reduce_final + combine_update
-// (one launch less per round), results bitwise unchanged.  (A variant that also folded stage 1 in,
-// with the last block of each chunk finishing it, paid a device-scope release fence per block --
-// an L2 writeback on every XCD -- and took 427 us: profiles/round3/fused_update.)
-// 1024 threads: 16 waves share a chunk's slots (the headline's 22 slots took ~6 dependent rounds of
-// split loads per wave at 4 waves, 10.2 us per call: profiles/round3/prof_nt).
-template <typename A>
-__global__ void __launch_bounds__(1024)
-slab_final_update(const A* __restrict__ part, A* __restrict__ G, int ld, int nslots, const LocalUpdate up) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lu_raw[];
-  A* gs = reinterpret_cast<A*>(lu_raw);  // [nslots][64] the chunk's message sums
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int c = blockIdx.x * kWave + lane;
-  if (up.stamp && blockIdx.x == 0 && threadIdx.x == 0) *up.stamp = wall_clock64();
-  for (int q = wid; q < nslots; q += static_cast<int>(blockDim.x >> 6)) {
-    A v = A(0);
-    if (c < ld) {
-#pragma unroll
-      for (int k = 0; k < kSplits; ++k) v += part[(static_cast<long long>(q) * kSplits + k) * ld + c];
-      G[static_cast<long long>(q) * ld + c] = v;
-    }
-    gs[q * kWave + lane] = v;
-  }
-  __syncthreads();
-  if (wid != 0 || c >= ld) return;
-  A* bw = static_cast<A*>(up.beta_w);
-  if (c >= up.d) {  // padded columns stay exactly zero
-    if (bw) bw[c] = A(0);
-    return;
-  }
-  double g = 0.0;  // combine_update: the fma chain in message order
-  for (int m = 0; m < up.nmsg; ++m) g = fma(up.coef[m], static_cast<double>(gs[up.slot[m] * kWave + lane]), g);
-  const double b = up.beta[c];
-  double nb;
-  if (up.rule == 0) {  // GD
-    nb = up.decay * b - up.gm * g;
-  } else {  // AGD
-    const double yt = (1.0 - up.theta) * b + up.theta * up.u[c];
-    nb = yt - up.gm * g - up.l2 * b;
-    up.u[c] = b + (nb - b) * (1.0 / up.theta);
-  }
-  up.beta[c] = nb;
-  if (up.hist) up.hist[c] = nb;
-  if (bw) bw[c] = static_cast<A>(nb);
-}
-
-template <typename A>
-static hipError_t slab_reduce_launch(const A* slab, const int* stb, A* part, A* G, int nslots, int ld,
-                                     hipStream_t st, const PutDesc* put = nullptr, const int* gate = nullptr) {
-  if (put && put->tag && (nslots > kMaxTagRows || !put->csum)) return hipErrorInvalidValue;
-  if (put && put->gate != gate) return hipErrorInvalidValue;  // one round, one gate
-  PutDesc pd{};
-  if (put) {  // the process's release form (launchers.h strict_release)
-    pd = *put;
-    pd.strict = strict_release() ? 1 : 0;
-    put = &pd;
-  }
-  const dim3 fgrid(ceil_div(ld, kWave), nslots);
-  if (g_slab_mode != 0 && !put) {  // both stages in one launch (bitwise the same sums)
-    hipLaunchKernelGGL(slab_reduce_fused<A>, fgrid, dim3(1024), 0, st, slab, stb, G, ld, gate);
-    return hipGetLastError();
-  }
-  if (g_slab_mode == 1 && put) {
-    hipLaunchKernelGGL(slab_reduce_fused_put<A>, fgrid, dim3(1024), 0, st, slab, stb, G, ld, *put);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(slab_reduce_partial<A>, dim3(ceil_div(ld, kWave), nslots, kSplits), dim3(256), 0, st,
-                     slab, stb, part, ld, gate);
-  if (put && nslots <= kPutOneSlots && static_cast<long long>(nslots) * ld <= kPutOneElems)
-    hipLaunchKernelGGL(slab_reduce_final_put1<A>, dim3(1), dim3(1024), 0, st, part, G, ld, nslots, *put);
-  else if (put)
-    hipLaunchKernelGGL(slab_reduce_final_put<A>, dim3(ceil_div(ld, 256), nslots), dim3(256), 0, st, part, G, ld, *put);
-  else
-    hipLaunchKernelGGL(slab_reduce_final<A>, dim3(ceil_div(ld, 256), nslots), dim3(256), 0, st, part, G, ld, gate);
-  return hipGetLastError();
-}
-
 // ----- Wide-feature fallback (d > 64 * 32): two passes over X, still no atomics. -----
 // Pass 1: one wave per row computes z = x_row . beta and stores the loss residual r.
 template <typename T, typename A, int LOSS>
@@ -1452,12 +1092,30 @@ xt_r_tiles(const Segment* __restrict__ segs, const Task* __restrict__ tasks,
 }  // namespace eh
 
 // ---------------------------------------------------------------------------------
-// Host launchers (called from bindings.cpp).
+// Host launchers (called from bindings.cpp and the native round executors).
 namespace eh {
 
-void set_slab_reduce_mode(int mode) { g_slab_mode = mode; }
+// Timeline probe of grad_dense_multi (set_grad_stamps; nullptr = off, every production launch).
+static long long* g_stamps = nullptr;
 void set_grad_stamps(void* stamps) { g_stamps = static_cast<long long*>(stamps); }
-int slab_reduce_mode() { return g_slab_mode; }
+
+// One wide-row launch at NV, NV / 2 or NV / 4 vectors per thread, the fewest that cover ld.
+// Rows that fill at most half of the NV vectors (fp32 d <= 4096 at 256 threads) take the NV / 2
+// instance: the unused half would still hold R + 3 register tiles (valid[] is a run-time mask),
+// which halves the resident workgroups per CU.  fp32 / bf16 rows of <= 2048 columns (32 per lane)
+// fit a quarter of the vectors.
+template <typename T, typename A, int NV, int BS, int LOSS, int R>
+static void launch_wide_nv(dim3 grid, hipStream_t st, const Segment* segs, const Task* tasks, const A* beta, A* slab,
+                           int ld, const int* gate) {
+  const bool half = static_cast<long long>(BS) * (NV / 2) * Vec16<T>::N >= ld;
+  const bool quarter = NV >= 8 && static_cast<long long>(BS) * (NV / 4) * Vec16<T>::N >= ld;
+  auto kern = grad_dense_wide<T, A, NV, BS, LOSS, R>;
+  if (quarter)
+    kern = grad_dense_wide<T, A, NV / 4, BS, LOSS, R>;
+  else if (half)
+    kern = grad_dense_wide<T, A, NV / 2, BS, LOSS, R>;
+  hipLaunchKernelGGL(kern, grid, dim3(BS), 0, st, segs, tasks, beta, slab, ld, gate);
+}
 
 // Wide kernel: 16 elements per thread per row for fp64 (NV = 8), 32 for fp32 (NV = 8) and
 // bf16 (NV = 4); the block size BS (256 / 512) covers ld.  (1024-thread blocks would cap a
@@ -1468,45 +1126,24 @@ static hipError_t launch_wide(int bs, int R, const Segment* segs, const Task* ta
   constexpr int NV = Vec16<T>::N == 8 ? 4 : 8;
   if (R < 1 || R > 3 || ntasks % R) return hipErrorInvalidValue;
   const dim3 grid(ntasks / R);
-  // Rows that fill at most half of the NV vectors (fp32 d <= 4096 at 256 threads) take the NV / 2
-  // instance: the unused half would still hold R + 3 register tiles (valid[] is a run-time mask),
-  // which halves the resident workgroups per CU.
   const bool half = static_cast<long long>(bs) * (NV / 2) * Vec16<T>::N >= ld;
-  // fp32 / bf16 rows of <= 2048 columns (32 per lane) fit a quarter of the vectors
-  const bool quarter = NV >= 8 && static_cast<long long>(bs) * (NV / 4) * Vec16<T>::N >= ld;
-#define EH_WIDE(NV_, BS_, R_)                                                                                     \
-  hipLaunchKernelGGL((grad_dense_wide<T, A, NV_, BS_, LOSS, R_>), grid, dim3(BS_), 0, st, segs, tasks, beta, slab, ld, \
-                     gate)
-#define EH_WIDE_NV(BS_, R_)       \
-  do {                            \
-    if (quarter)                  \
-      EH_WIDE(NV / 4, BS_, R_);   \
-    else if (half)                \
-      EH_WIDE(NV / 2, BS_, R_);   \
-    else                          \
-      EH_WIDE(NV, BS_, R_);       \
-  } while (0)
   if (bs == 256 && R > 1 && !half) {
     // Replica bundles of full-width rows: 512 threads of NV / 2 vectors cover the same columns.  The
     // 256-thread NV instance holds R + 3 tiles of 2 NV values per thread (fp64 R = 3: 256 VGPRs plus
     // AGPR spills, 1 wave per SIMD); at 512 threads the tiles halve (150 VGPRs) and a CU keeps 8 waves
     // of the bundle in flight instead of 4.  One such workgroup is resident per CU
     // (ops/grad.py wide_slots_per_cu).
-    if (R == 2)
-      hipLaunchKernelGGL((grad_dense_wide<T, A, NV / 2, 512, LOSS, 2, true>), grid, dim3(512), 0, st, segs, tasks, beta,
-                         slab, ld, gate);
-    else
-      hipLaunchKernelGGL((grad_dense_wide<T, A, NV / 2, 512, LOSS, 3, true>), grid, dim3(512), 0, st, segs, tasks, beta,
-                         slab, ld, gate);
+    auto kern = R == 2 ? grad_dense_wide<T, A, NV / 2, 512, LOSS, 2, true> : grad_dense_wide<T, A, NV / 2, 512, LOSS, 3, true>;
+    hipLaunchKernelGGL(kern, grid, dim3(512), 0, st, segs, tasks, beta, slab, ld, gate);
   } else if (bs == 256) {
-    if (R == 1) EH_WIDE_NV(256, 1); else if (R == 2) EH_WIDE_NV(256, 2); else EH_WIDE_NV(256, 3);
+    if (R == 1) launch_wide_nv<T, A, NV, 256, LOSS, 1>(grid, st, segs, tasks, beta, slab, ld, gate);
+    else if (R == 2) launch_wide_nv<T, A, NV, 256, LOSS, 2>(grid, st, segs, tasks, beta, slab, ld, gate);
+    else launch_wide_nv<T, A, NV, 256, LOSS, 3>(grid, st, segs, tasks, beta, slab, ld, gate);
   } else if (bs == 512 && R == 1) {  // (replica bundles of 512-thread rows would spill: R * 16+ accumulators)
-    EH_WIDE_NV(512, 1);
+    launch_wide_nv<T, A, NV, 512, LOSS, 1>(grid, st, segs, tasks, beta, slab, ld, gate);
   } else {
     return hipErrorInvalidValue;
   }
-#undef EH_WIDE_NV
-#undef EH_WIDE
   return hipGetLastError();
 }
 
@@ -1537,10 +1174,60 @@ static hipError_t launch_multi(bool fold, bool lane_epi, bool pair, dim3 grid, d
   return hipGetLastError();
 }
 
+// The narrow-row kernels (staged, multi, fused) at C columns per lane; C must be a multiple of the
+// 16-byte vector width, and the one-wave bundles hold at most 16 columns per lane.
+template <typename T, typename A, int C, int LOSS>
+static hipError_t launch_cpl(const Segment* segs, const Task* tasks, int ntasks, const A* beta, A* slab, int ld,
+                             hipStream_t st, const KernelChoice& k, const StagedGeom& sg, const int* gate) {
+  if constexpr (C % Vec16<T>::N != 0) {
+    return hipErrorInvalidValue;
+  } else {
+    const int R = k.replicas;
+    if (k.kind == kGradStaged) {  // rows streamed once through an LDS ring, one wave per replica
+      auto kern = k.pair ? grad_dense_staged<T, A, C, LOSS, true> : grad_dense_staged<T, A, C, LOSS, false>;
+      if (sg.lds > 65536) {
+        const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sg.lds));
+        if (ea != hipSuccess) return ea;
+      }
+      hipLaunchKernelGGL(kern, dim3(ntasks / R), dim3(64 * R * sg.wpr), sg.lds, st, segs, tasks, beta, slab, ld,
+                         sg.srows, sg.pieces, sg.nstage, sg.wpr, gate);
+      return hipGetLastError();
+    }
+    if (k.kind == kGradMulti) {  // every replica of a bundle in one wave, rows in registers
+      if constexpr (C <= 16) {
+        const int nb = ntasks / R;
+        if (k.fold && nb % 4) return hipErrorInvalidValue;
+        const dim3 mg((nb + 3) / 4), mb(256);
+        const bool f = k.fold != 0, le = k.lane_epi != 0, pr = k.pair != 0;
+        if (R == 1) return launch_multi<T, A, C, LOSS, 1>(f, le, pr, mg, mb, st, segs, tasks, nb, beta, slab, ld, gate);
+        if (R == 2) return launch_multi<T, A, C, LOSS, 2>(f, le, pr, mg, mb, st, segs, tasks, nb, beta, slab, ld, gate);
+        if (R == 3) return launch_multi<T, A, C, LOSS, 3>(f, le, pr, mg, mb, st, segs, tasks, nb, beta, slab, ld, gate);
+      }
+      return hipErrorInvalidValue;
+    }
+    // fused: a wave per row, k.rows rows in flight (2: the interleaved pair kernel), beta in registers or LDS
+    const dim3 grid(ntasks), block(256);
+    const size_t sh = 4ull * kWave * C * sizeof(A);
+    const size_t shb = sh + kWave * C * sizeof(A);
+    auto kern = grad_dense_fused_pair<T, A, C, LOSS>;
+    if (k.beta_lds)
+      kern = k.rows == 1   ? grad_dense_fused<T, A, C, LOSS, 1, true>
+             : k.rows == 2 ? grad_dense_fused<T, A, C, LOSS, 2, true>
+                           : grad_dense_fused<T, A, C, LOSS, 4, true>;
+    else if (k.rows == 1)
+      kern = grad_dense_fused<T, A, C, LOSS, 1>;
+    else if (k.rows == 4)
+      kern = grad_dense_fused<T, A, C, LOSS, 4>;
+    hipLaunchKernelGGL(kern, grid, block, k.beta_lds ? shb : sh, st, segs, tasks, beta, slab, ld, gate);
+    return hipGetLastError();
+  }
+}
+
 template <typename T, typename A, int LOSS>
 static hipError_t launch_fused_cpl(int cpl, const Segment* segs, const Task* tasks, int ntasks,
                                    const A* beta, A* slab, int ld, hipStream_t st, const KernelChoice& k,
-                                   const int* gate = nullptr) {
+                                   const int* gate) {
   if (k.kind == kGradMfma) {  // bf16 replica bundles on the matrix cores (grad_mfma.hip)
     if constexpr (std::is_same<T, bf16_t>::value)
       return grad_mfma_launch(LOSS, segs, tasks, ntasks, k.replicas, beta, slab, ld, st, gate);
@@ -1556,90 +1243,39 @@ static hipError_t launch_fused_cpl(int cpl, const Segment* segs, const Task* tas
   if (k.kind == kGradStaged &&
       (R > 8 || !staged_geometry(R, ld * static_cast<int>(sizeof(T)), 64ull * cpl * sizeof(A), &sg, k.wpr)))
     return hipErrorInvalidValue;
-  constexpr int VN = Vec16<T>::N;
-  const dim3 block(256);
-  const dim3 grid(ntasks);
-  // CPL (columns per lane) must be a multiple of the 16-byte vector width VN.
-#define EH_IF(C)                                                                                       \
-  case C:                                                                                              \
-    if constexpr (C % VN == 0) {                                                                       \
-      if (k.kind == kGradStaged) { /* rows streamed once through an LDS ring, one wave per replica */  \
-        auto kern = k.pair ? grad_dense_staged<T, A, C, LOSS, true> : grad_dense_staged<T, A, C, LOSS, false>; \
-        if (sg.lds > 65536) {                                                                          \
-          const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                \
-              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sg.lds));                   \
-          if (ea != hipSuccess) return ea;                                                             \
-        }                                                                                              \
-        hipLaunchKernelGGL(kern, dim3(ntasks / R), dim3(64 * R * sg.wpr), sg.lds, st, segs, tasks, beta, \
-                           slab, ld, sg.srows, sg.pieces, sg.nstage, sg.wpr, gate);                    \
-        return hipGetLastError();                                                                      \
-      }                                                                                                \
-      if (k.kind == kGradMulti) { /* every replica of a bundle in one wave, rows in registers */       \
-        if constexpr (C <= 16) {                                                                       \
-          const int nb_ = ntasks / R;                                                                  \
-          if (k.fold && nb_ % 4) return hipErrorInvalidValue;                                          \
-          const dim3 mg((nb_ + 3) / 4), mb(256);                                                       \
-          const bool f = k.fold != 0, le = k.lane_epi != 0, pr = k.pair != 0;                          \
-          if (R == 1) return launch_multi<T, A, C, LOSS, 1>(f, le, pr, mg, mb, st, segs, tasks, nb_, beta, slab, ld, gate); \
-          if (R == 2) return launch_multi<T, A, C, LOSS, 2>(f, le, pr, mg, mb, st, segs, tasks, nb_, beta, slab, ld, gate); \
-          if (R == 3) return launch_multi<T, A, C, LOSS, 3>(f, le, pr, mg, mb, st, segs, tasks, nb_, beta, slab, ld, gate); \
-        }                                                                                              \
-        return hipErrorInvalidValue;                                                                   \
-      }                                                                                                \
-      /* fused: a wave per row, k.rows rows in flight (2: the interleaved pair kernel), beta in      \
-         registers or LDS */                                                                           \
-      const size_t sh = 4ull * kWave * C * sizeof(A);                                                  \
-      const size_t shb = sh + kWave * C * sizeof(A);                                                   \
-      if (k.beta_lds) {                                                                                \
-        if (k.rows == 1)                                                                               \
-          hipLaunchKernelGGL((grad_dense_fused<T, A, C, LOSS, 1, true>), grid, block, shb, st, segs, tasks, beta, slab, ld, gate); \
-        else if (k.rows == 2)                                                                          \
-          hipLaunchKernelGGL((grad_dense_fused<T, A, C, LOSS, 2, true>), grid, block, shb, st, segs, tasks, beta, slab, ld, gate); \
-        else                                                                                           \
-          hipLaunchKernelGGL((grad_dense_fused<T, A, C, LOSS, 4, true>), grid, block, shb, st, segs, tasks, beta, slab, ld, gate); \
-      } else if (k.rows == 1) {                                                                        \
-        hipLaunchKernelGGL((grad_dense_fused<T, A, C, LOSS, 1>), grid, block, sh, st, segs, tasks, beta, slab, ld, gate); \
-      } else if (k.rows == 4) {                                                                        \
-        hipLaunchKernelGGL((grad_dense_fused<T, A, C, LOSS, 4>), grid, block, sh, st, segs, tasks, beta, slab, ld, gate); \
-      } else {                                                                                         \
-        hipLaunchKernelGGL((grad_dense_fused_pair<T, A, C, LOSS>), grid, block, sh, st, segs, tasks, beta, slab, ld, gate); \
-      }                                                                                                \
-      return hipGetLastError();                                                                        \
-    } else {                                                                                           \
-      return hipErrorInvalidValue;                                                                     \
-    }
   switch (cpl) {
-    EH_IF(2)
-    EH_IF(4)
-    EH_IF(8)
-    EH_IF(16)
-    EH_IF(32)
-    default:
-      return hipErrorInvalidValue;
+    case 2: return launch_cpl<T, A, 2, LOSS>(segs, tasks, ntasks, beta, slab, ld, st, k, sg, gate);
+    case 4: return launch_cpl<T, A, 4, LOSS>(segs, tasks, ntasks, beta, slab, ld, st, k, sg, gate);
+    case 8: return launch_cpl<T, A, 8, LOSS>(segs, tasks, ntasks, beta, slab, ld, st, k, sg, gate);
+    case 16: return launch_cpl<T, A, 16, LOSS>(segs, tasks, ntasks, beta, slab, ld, st, k, sg, gate);
+    case 32: return launch_cpl<T, A, 32, LOSS>(segs, tasks, ntasks, beta, slab, ld, st, k, sg, gate);
+    default: return hipErrorInvalidValue;
   }
-#undef EH_IF
 }
 
-// dtype codes: 0 = fp64 storage/fp64 acc, 1 = fp32/fp32, 2 = bf16 storage/fp32 acc
+// The gradient kernel the plan chose, for the launch's loss and storage codes: one slab row per task.
+static hipError_t launch_gradient(int dtype, int loss, int cpl, const void* segs, const void* tasks, int ntasks,
+                                  const void* beta, void* slab, int ld, hipStream_t st, const KernelChoice& k,
+                                  const int* gate) {
+  const Segment* S = static_cast<const Segment*>(segs);
+  const Task* Tk = static_cast<const Task*>(tasks);
+  return dispatch_loss(loss, [&](auto L) {
+    return dispatch_storage(dtype, [&](auto D) {
+      using T = typename decltype(D)::T;
+      using A = typename decltype(D)::A;
+      return launch_fused_cpl<T, A, decltype(L)::value>(cpl, S, Tk, ntasks, (const A*)beta, (A*)slab, ld, st, k, gate);
+    });
+  });
+}
+
 hipError_t grad_dense_launch(int dtype, int loss, int cpl, const void* segs, const void* tasks,
                              int ntasks, const void* beta, void* slab, const int* slot_task_begin,
                              int nslots, void* part, void* G, int ld, hipStream_t st, const KernelChoice& k,
                              const PutDesc* put, const int* gate) {
-  const Segment* S = static_cast<const Segment*>(segs);
-  const Task* Tk = static_cast<const Task*>(tasks);
-  const hipError_t e = dispatch_loss(loss, [&](auto L) {
-    constexpr int kL = decltype(L)::value;
-    if (dtype == 0)
-      return launch_fused_cpl<double, double, kL>(cpl, S, Tk, ntasks, (const double*)beta, (double*)slab, ld, st, k, gate);
-    if (dtype == 1)
-      return launch_fused_cpl<float, float, kL>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k, gate);
-    return launch_fused_cpl<bf16_t, float, kL>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k, gate);
-  });
+  const hipError_t e = launch_gradient(dtype, loss, cpl, segs, tasks, ntasks, beta, slab, ld, st, k, gate);
   if (e != hipSuccess) return e;
-  if (dtype == 0) return slab_reduce_launch<double>((const double*)slab, slot_task_begin, (double*)part, (double*)G, nslots, ld, st, put, gate);
-  return slab_reduce_launch<float>((const float*)slab, slot_task_begin, (float*)part, (float*)G, nslots, ld, st, put, gate);
+  return slab_reduce_launch(dtype, slab, slot_task_begin, part, G, nslots, ld, st, put, gate);
 }
-
 
 hipError_t grad_dense_update_launch(int dtype, int loss, int cpl, const void* segs, const void* tasks, int ntasks,
                                     const void* beta, void* slab, const int* stb, int nslots, void* part, void* G,
@@ -1647,35 +1283,9 @@ hipError_t grad_dense_update_launch(int dtype, int loss, int cpl, const void* se
   if (nslots < 1 || nslots > kMaxMsgs || up.nmsg < 0 || up.nmsg > kMaxMsgs || !up.beta) return hipErrorInvalidValue;
   for (int m = 0; m < up.nmsg; ++m)
     if (up.slot[m] < 0 || up.slot[m] >= nslots) return hipErrorInvalidValue;
-  const Segment* S = static_cast<const Segment*>(segs);
-  const Task* Tk = static_cast<const Task*>(tasks);
-  hipError_t e = dispatch_loss(loss, [&](auto L) {
-    constexpr int kL = decltype(L)::value;
-    if (dtype == 0)
-      return launch_fused_cpl<double, double, kL>(cpl, S, Tk, ntasks, (const double*)beta, (double*)slab, ld, st, k);
-    if (dtype == 1)
-      return launch_fused_cpl<float, float, kL>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k);
-    return launch_fused_cpl<bf16_t, float, kL>(cpl, S, Tk, ntasks, (const float*)beta, (float*)slab, ld, st, k);
-  });
+  const hipError_t e = launch_gradient(dtype, loss, cpl, segs, tasks, ntasks, beta, slab, ld, st, k, nullptr);
   if (e != hipSuccess) return e;
-  const dim3 pgrid(ceil_div(ld, kWave), nslots, kSplits);
-  const size_t lds = static_cast<size_t>(nslots) * kWave * (dtype == 0 ? 8 : 4);
-  auto go = [&](const void* kern) -> hipError_t {
-    if (lds <= 60 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-  };
-  if (dtype == 0) {
-    hipLaunchKernelGGL(slab_reduce_partial<double>, pgrid, dim3(256), 0, st, (const double*)slab, stb, (double*)part, ld, nullptr);
-    if ((e = go(reinterpret_cast<const void*>(slab_final_update<double>))) != hipSuccess) return e;
-    hipLaunchKernelGGL(slab_final_update<double>, dim3(ceil_div(ld, kWave)), dim3(1024), lds, st, (const double*)part,
-                       (double*)G, ld, nslots, up);
-  } else {
-    hipLaunchKernelGGL(slab_reduce_partial<float>, pgrid, dim3(256), 0, st, (const float*)slab, stb, (float*)part, ld, nullptr);
-    if ((e = go(reinterpret_cast<const void*>(slab_final_update<float>))) != hipSuccess) return e;
-    hipLaunchKernelGGL(slab_final_update<float>, dim3(ceil_div(ld, kWave)), dim3(1024), lds, st, (const float*)part,
-                       (float*)G, ld, nslots, up);
-  }
-  return hipGetLastError();
+  return slab_reduce_update_launch(dtype, slab, stb, part, G, nslots, ld, st, up);
 }
 
 hipError_t grad_dense_twopass_launch(int dtype, int loss, const void* segs, const void* tasks,
@@ -1685,27 +1295,19 @@ hipError_t grad_dense_twopass_launch(int dtype, int loss, const void* segs, cons
   const Segment* S = static_cast<const Segment*>(segs);
   const Task* Tk = static_cast<const Task*>(tasks);
   const dim3 block(256);
-  const hipError_t el = dispatch_loss(loss, [&](auto L) {
-    constexpr int kL = decltype(L)::value;
-    if (dtype == 0)
-      hipLaunchKernelGGL((rowdot_residual<double, double, kL>), dim3(ntasks), block, 0, st, S, Tk, (const double*)beta, task_row_off, (double*)rbuf, ld, gate);
-    else if (dtype == 1)
-      hipLaunchKernelGGL((rowdot_residual<float, float, kL>), dim3(ntasks), block, 0, st, S, Tk, (const float*)beta, task_row_off, (float*)rbuf, ld, gate);
-    else
-      hipLaunchKernelGGL((rowdot_residual<bf16_t, float, kL>), dim3(ntasks), block, 0, st, S, Tk, (const float*)beta, task_row_off, (float*)rbuf, ld, gate);
-    return hipSuccess;
+  const hipError_t e = dispatch_loss(loss, [&](auto L) {
+    return dispatch_storage(dtype, [&](auto D) {
+      using T = typename decltype(D)::T;
+      using A = typename decltype(D)::A;
+      hipLaunchKernelGGL((rowdot_residual<T, A, decltype(L)::value>), dim3(ntasks), block, 0, st, S, Tk,
+                         static_cast<const A*>(beta), task_row_off, static_cast<A*>(rbuf), ld, gate);
+      hipLaunchKernelGGL((xt_r_tiles<T, A>), dim3(ntasks, ceil_div(ld, 256 * Vec16<T>::N)), block, 0, st, S, Tk,
+                         task_row_off, static_cast<const A*>(rbuf), static_cast<A*>(slab), ld, gate);
+      return hipGetLastError();
+    });
   });
-  if (el != hipSuccess) return el;
-  if (dtype == 0)
-    hipLaunchKernelGGL((xt_r_tiles<double, double>), dim3(ntasks, ceil_div(ld, 256 * 2)), block, 0, st, S, Tk, task_row_off, (const double*)rbuf, (double*)slab, ld, gate);
-  else if (dtype == 1)
-    hipLaunchKernelGGL((xt_r_tiles<float, float>), dim3(ntasks, ceil_div(ld, 256 * 4)), block, 0, st, S, Tk, task_row_off, (const float*)rbuf, (float*)slab, ld, gate);
-  else
-    hipLaunchKernelGGL((xt_r_tiles<bf16_t, float>), dim3(ntasks, ceil_div(ld, 256 * 8)), block, 0, st, S, Tk, task_row_off, (const float*)rbuf, (float*)slab, ld, gate);
-  hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if (dtype == 0) return slab_reduce_launch<double>((const double*)slab, slot_task_begin, (double*)part, (double*)G, nslots, ld, st, nullptr, gate);
-  return slab_reduce_launch<float>((const float*)slab, slot_task_begin, (float*)part, (float*)G, nslots, ld, st, nullptr, gate);
+  return slab_reduce_launch(dtype, slab, slot_task_begin, part, G, nslots, ld, st, nullptr, gate);
 }
 
 }  // namespace eh

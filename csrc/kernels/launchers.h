@@ -22,19 +22,19 @@ namespace eh {
 bool strict_release();
 void set_release_form(bool strict);
 
-// ---- worker gradient (grad_dense.hip, grad_sparse.hip) -------------------------------
+// ---- worker gradient (grad_dense.hip + slab_reduce.hip, grad_sparse.hip) ---------------
 // dtype: 0 fp64 storage/acc, 1 fp32/fp32, 2 bf16 storage/fp32 acc; loss: 0 logistic, 1 least squares
 // k: the kernel the plan chose (grad_dense.h KernelChoice)
 // Slab-reduction scratch of the dense launchers ("part"): [nslots][kSlabSplits][ld] partial sums in
 // the accumulator type.
-constexpr long long kSlabSplits = 16;  // grad_dense.hip kSplits
+constexpr long long kSlabSplits = 16;  // splits per message of the slab reduction's stage 1 (slab_reduce.hip)
 inline long long slab_part_bytes(long long nslots, long long ld, long long acc_bytes) {
   return nslots * kSlabSplits * ld * acc_bytes;
 }
 
 struct PutDesc;
 struct KernelChoice;
-// Slab reduction form (grad_dense.hip g_slab_mode): 1 fused launches (default), 2 fused plain /
+// Slab reduction form (slab_reduce.hip g_slab_mode): 1 fused launches (default), 2 fused plain /
 // two-stage puts, 0 two stages.
 void set_slab_reduce_mode(int mode);
 // rows per LDS stage of the bf16 MFMA bundles (grad_mfma.hip): 32 (default) or 16 (a 4-deep ring), for A/B
@@ -179,7 +179,7 @@ struct LocalUpdate {
   int d, rule;
   double decay, gm, l2, theta;
 };
-// Gradient + slab reduction + combine + GD/AGD update in three launches (grad_dense.hip
+// Gradient + slab reduction + combine + GD/AGD update in three launches (slab_reduce.hip
 // slab_final_update); bitwise equal to grad_dense_launch followed by combine_update_launch.
 hipError_t grad_dense_update_launch(int dtype, int loss, int cpl, const void* segs, const void* tasks, int ntasks,
                                     const void* beta, void* slab, const int* slot_task_begin, int nslots, void* part,
@@ -228,7 +228,7 @@ struct PutDesc {
   const unsigned long long* beta_flag;
   unsigned long long stale_next;
   int strict;  // set by the launchers from strict_release() (common.h block_release_system)
-  // Landing stamp (nullptr = off): the last block writes {value, wall_clock64} here just before the
+  // Landing stamp (nullptr = off; put_protocol.h put_stamp): the last block writes {value, wall_clock64} here just before the
   // flag's release, so a receiver that sees the flag at `value` reads when that put landed on the
   // sender's clock (the collector orders physically late ranks' messages by it: csrc/runtime/
   // collector.h "Device times"); the value tells a slot of this round from one an older round (or a
@@ -237,25 +237,6 @@ struct PutDesc {
   long long* stamp;
   long long* stamp_log;
 };
-#if defined(__HIPCC__)
-// The landing stamp of a put (one thread of the last block, before the release that precedes the flag).
-__device__ __forceinline__ void put_stamp(const PutDesc& p) {
-  if (!p.stamp && !p.stamp_log) return;
-  const long long t = static_cast<long long>(wall_clock64());
-  if (p.stamp) {
-    p.stamp[0] = static_cast<long long>(p.value);
-    p.stamp[1] = t;
-  }
-  if (p.stamp_log) *p.stamp_log = t;
-}
-// The next round's gate word (one thread of the launch calls it).
-__device__ __forceinline__ void put_decide_next_gate(const PutDesc& p) {
-  if (!p.next_gate) return;
-  const unsigned long long b =
-      __hip_atomic_load(const_cast<unsigned long long*>(p.beta_flag), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(p.next_gate, b >= p.stale_next ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-#endif
 struct PutArgs {
   PutDesc d[kMaxPuts];
   int n;

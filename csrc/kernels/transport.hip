@@ -7,12 +7,9 @@
 // and then announced by a 64-bit generation flag in shared host memory that the
 // receiver's host polls (csrc/runtime/collector.cpp flag probes / ipc.cpp).
 //
-// Ordering (the classic put + signal pattern): every block copies its chunk with
-// 16-byte loads/stores, makes its writes visible at system scope (block_release_system:
-// every wave waits for its stores, one lane writes the L2 back), and counts itself done on
-// a per-descriptor counter; the last block of a descriptor resets the counter, releases its
-// tags the same way and stores the flag.  So a receiver that observes flag >= value also observes the payload, without
-// relying on kernel-boundary cache semantics across devices.
+// Ordering (the classic put + signal pattern): every block copies its chunk with 16-byte
+// loads/stores and then follows put_protocol.h, one descriptor per blockIdx.y: release, count, and
+// the last block of a descriptor writes the tags and announces the flag.
 //
 // Integrity (integrity.h): a tagged descriptor also checksums every row it copies (LDS sums per
 // row, one global add per row and block into the sender's scratch) and the last block writes
@@ -21,14 +18,11 @@
 
 #include "common.h"
 #include "launchers.h"
+#include "put_protocol.h"
 
 namespace eh {
 
 namespace {
-__device__ __forceinline__ bool aborted(const int* abort) {
-  return abort && __hip_atomic_load(abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
-}
-
 // Terms of one 16-byte vector of a row (es-byte elements starting at element j0).
 __device__ __forceinline__ unsigned long long vec_terms(const uint4& v, int es, long long j0) {
   if (es == 8) {
@@ -42,17 +36,14 @@ __device__ __forceinline__ unsigned long long vec_terms(const uint4& v, int es, 
 
 __global__ void __launch_bounds__(256) put_signal(PutArgs args) {
   __shared__ unsigned long long row_sum[kMaxTagRows];
-  __shared__ int s_last, s_abort;
+  __shared__ int s_last, s_live;
   const int k = blockIdx.y;
   if (k >= args.n) return;
   const PutDesc& p = args.d[k];
-  if (gate_closed(p.gate)) {  // a skipped stale round (launch-uniform): decide the next one's gate
-    if (blockIdx.x == 0 && threadIdx.x == 0) put_decide_next_gate(p);
-    return;
-  }
-  if (threadIdx.x == 0) s_abort = aborted(p.abort);  // one read, shared by the block
+  if (put_skipped(p, blockIdx.x == 0 && threadIdx.x == 0)) return;
+  if (threadIdx.x == 0) s_live = put_is_live(p);
   __syncthreads();
-  if (s_abort) return;  // the pump gave up: nothing is put or announced
+  if (!s_live) return;  // block-uniform
   const bool tagged = p.tag != nullptr;
   const long long nvec = p.bytes / 16;
   const long long row_vec = tagged ? nvec / p.rows : 1;  // 16-byte vectors per row
@@ -90,29 +81,9 @@ __global__ void __launch_bounds__(256) put_signal(PutArgs args) {
     for (int r = threadIdx.x; r < p.rows; r += blockDim.x)
       if (row_sum[r]) atomicAdd(p.csum + r, row_sum[r]);
   }
-  block_release_system(p.strict);  // this block's rows (and checksum adds) are out before its count
-  if (threadIdx.x == 0) {
-    // relaxed: the release above ordered the block's stores; the last block reads only the
-    // checksum sums, which are L2 atomics
-    const unsigned int prev = count_block_done(p.counter, p.strict);
-    s_last = prev == gridDim.x - 1;
-    if (s_last) __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (!s_last) return;  // block-uniform
-  if (tagged) {
-    for (int r = threadIdx.x; r < p.rows; r += blockDim.x) {
-      const unsigned long long sum = atomicExch(p.csum + r, 0ull);  // every block's adds are in
-      p.tag[r] = MsgTag{static_cast<unsigned int>(p.value), p.rank, sum};
-    }
-    if (p.corrupt && threadIdx.x == 0) static_cast<unsigned char*>(p.dst)[1] ^= 0x10;  // test hook
-  }
-  if (threadIdx.x == 0) put_stamp(p);
-  block_release_system(p.strict);  // the tags (and the landing stamp) before the flag
-  if (threadIdx.x == 0) {
-    publish_u64(p.flag, p.value, p.strict);
-    put_decide_next_gate(p);
-  }
+  if (!put_block_is_last(p, gridDim.x, &s_last)) return;  // block-uniform
+  put_tags_from_csum(p, p.rows);
+  put_publish(p);
 }
 
 // Signal only (no payload): flag = value once all prior work on the stream is done.

@@ -142,7 +142,7 @@ struct GradLauncher {
   }
 
   // Dense fused plans without device encoding can hand their result rows straight to the
-  // receiver's mailbox from the final reduction kernel (grad_dense.hip slab_reduce_final_put).
+  // receiver's mailbox from the final reduction kernel (slab_reduce.hip slab_reduce_fused_put / _final_put).
   bool can_fuse_put(int rows) const { return kind == 0 && !Gb && ntasks > 0 && nslots == rows; }
   // Device-driven local rounds: the combine + update ride the slab reduction (grad_dense_update_launch).
   bool can_fuse_update() const { return kind == 0 && !Gb && ntasks > 0; }
@@ -2288,7 +2288,36 @@ void bind_engine(py::module& m) {
                             gate ? gate->data_ptr<int>() : nullptr),
                    "GradLauncher.launch");
           },
-          py::arg("beta"), py::arg("G"), py::arg("gate") = py::none());
+          py::arg("beta"), py::arg("G"), py::arg("gate") = py::none())
+      // The gradient with its tagged put fused into the slab reduction (launch_put), for the kernel
+      // tests: the same descriptor as ipc.cpp put_signal_tagged; the worker pump builds its own natively.
+      .def(
+          "launch_put_tagged",
+          [](const GradLauncher& g, const Tensor& beta, const Tensor& G, const Tensor& dst, const Tensor& tags,
+             uintptr_t flag, uint64_t value, int64_t rank, const Tensor& counters, const Tensor& csum, bool corrupt) {
+            for (auto* t : {&beta, &G, &dst, &tags, &counters, &csum}) need_gpu(*t, "launch_put_tagged operand");
+            need(G.dim() == 2 && g.can_fuse_put((int)G.size(0)) && G.size(1) == g.ld && acc_code(G) == g.acc,
+                 "launch_put_tagged: a dense fused plan and its [nslots, ld] message buffer");
+            need(dst.sizes() == G.sizes() && dst.scalar_type() == G.scalar_type(), "launch_put_tagged: dst like G");
+            need(G.size(0) <= eh::kMaxTagRows && tags.numel() * tags.element_size() >= G.size(0) * 16 &&
+                     csum.scalar_type() == at::kLong && csum.numel() >= G.size(0) &&
+                     counters.scalar_type() == at::kInt && counters.numel() >= 1 && flag != 0,
+                 "launch_put_tagged: tags [rows*16 bytes], csum int64 [rows], counters int32, a flag");
+            eh::PutDesc d{G.data_ptr(), dst.data_ptr(), G.numel() * G.element_size(),
+                          reinterpret_cast<unsigned long long*>(flag), value,
+                          reinterpret_cast<unsigned int*>(counters.data_ptr<int>())};
+            d.tag = static_cast<eh::MsgTag*>(tags.data_ptr());
+            d.csum = reinterpret_cast<unsigned long long*>(csum.data_ptr<int64_t>());
+            d.rows = (int)G.size(0);
+            d.es = (int)G.element_size();
+            d.rank = static_cast<unsigned int>(rank);
+            d.corrupt = corrupt ? 1 : 0;
+            hcheck(g.launch_put(beta.data_ptr(), G.data_ptr(), d,
+                                c10::hip::getCurrentHIPStream(G.device().index()).stream()),
+                   "GradLauncher.launch_put_tagged");
+          },
+          py::arg("beta"), py::arg("G"), py::arg("dst"), py::arg("tags"), py::arg("flag"), py::arg("value"),
+          py::arg("rank"), py::arg("counters"), py::arg("csum"), py::arg("corrupt") = false);
   py::class_<MasterPump>(m, "MasterPump")
       .def(py::init<eh::Collector*, int, int, int, int, int, int, double>(), py::arg("collector"), py::arg("W"),
            py::arg("R"), py::arg("K"), py::arg("d"), py::arg("ld"), py::arg("device"), py::arg("timeout"),

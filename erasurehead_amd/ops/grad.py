@@ -33,7 +33,7 @@ DEFAULT_TASKS = 2048
 REPLICA_TASKS = 4096
 MAX_BUNDLE = 8  # replica task slots (waves) per workgroup of grad_dense_staged
 MIN_ROWS_PER_TASK = 32
-SLAB_SPLITS = 16  # csrc/kernels/grad_dense.hip kSplits
+SLAB_SPLITS = 16  # csrc/kernels/launchers.h kSlabSplits
 N_CUS = 256  # MI355X compute units (8 XCDs x 32)
 # A rank streams in the "long-stream" regime when each CU reads at least this many distinct rows per
 # round: there the gradient is HBM-bound with fewer, longer bundles (their per-bundle beta load,

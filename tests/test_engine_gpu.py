@@ -89,7 +89,7 @@ def test_gpu_device_loop_timed_segments(native):
 @pytest.mark.parametrize("case", [(1, 0, 3, 7, 2, 4), (1, 0, 0, 7, 2, 0), (0, 0, 0, 5, 0, 0)])
 def test_gpu_fused_update_is_bitwise_identical(case, precision, mode, native):
     """Device-driven local rounds with the combine + update inside the slab reduction
-    (grad_dense.hip slab_reduce_update) give bitwise the betas of the separate slab_reduce_final +
+    (slab_reduce.hip slab_final_update) give bitwise the betas of the separate slab_reduce_final +
     combine_update launches, AGD and GD, fp64 and fp32 messages, d not a multiple of the 64-column
     chunk."""
     is_coded, P, ver, n_procs, s, k = case

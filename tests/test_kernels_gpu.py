@@ -1,5 +1,6 @@
 """Numerics of the gfx950 HIP kernels against fp64 NumPy/PyTorch references (GPU only)."""
 import collections
+import uuid
 
 import numpy as np
 import pytest
@@ -421,6 +422,55 @@ def test_fused_slab_reduction_is_bitwise_the_two_stages(prec_name, d, rows, nati
         C.set_slab_reduce_mode(1)
     assert torch.equal(out[0], out[1])
     assert torch.count_nonzero(out[1]) > 0
+
+
+@pytest.mark.parametrize("prec_name", ["fp64", "fp32"])
+@pytest.mark.parametrize("nmsg", [3, 6])
+def test_slab_reduction_put_forms_agree(prec_name, nmsg, native):
+    """The tagged put fused into the slab reduction, in every slab mode: 1 = slab_reduce_fused_put; 0 and 2 =
+    stage 1 + slab_reduce_final_put1 (3 messages: nslots * ld <= 4096 elements, one block) or
+    slab_reduce_final_put (6 messages).  Each form writes the plain run's bits to G and to the receiver's
+    rows, tags that verify, the flag, and leaves the sender scratch zero; the corrupt hook is caught."""
+    C = native
+    prec = get_precision(prec_name)
+    rng = np.random.RandomState(17)
+    parts, _ = _parts(rng, [300, 200, 100], 1000, prec)
+    msgs = [[(0, 1.0), (1, 1.0)], [(1, 0.5), (2, -1.0)], [(2, 1.0)]] * (nmsg // 3)
+    plan = DenseGradPlan(msgs, parts, prec, LOGISTIC, 1000, choice=MESSAGE_MAJOR)
+    assert (nmsg * plan.ld <= 4096) == (nmsg == 3)
+    beta = torch.randn(plan.ld, dtype=prec.acc, device=DEV) * 0.05
+    want = plan.out_buffer()[0]
+    plan.run(beta, want)
+    torch.cuda.synchronize()
+    assert torch.count_nonzero(want) > 0
+    L = plan.native_launcher()
+    flags = C.ShmFlags("/eh_t_" + uuid.uuid4().hex[:12], 2, True)
+    counters = torch.zeros(64, dtype=torch.int32, device=DEV)
+    csum = torch.zeros(64, dtype=torch.int64, device=DEV)
+
+    def put(value, corrupt=False):
+        G, dst = plan.out_buffer()[0], plan.out_buffer()[0]
+        tags = torch.zeros(nmsg * 16, dtype=torch.uint8, device=DEV)
+        L.launch_put_tagged(beta, G, dst, tags, flags.dev_addr(0), value, 3, counters, csum, corrupt=corrupt)
+        torch.cuda.synchronize()
+        return G, dst, tags
+
+    try:
+        for mode in (0, 1, 2):
+            C.set_slab_reduce_mode(mode)
+            value = 7 + mode
+            G, dst, tags = put(value)
+            assert torch.equal(G, want), mode
+            assert torch.equal(dst, G), mode
+            assert C.verify_rows(dst, tags, value, 3) == {}, mode
+            assert flags.load(0) == value, mode
+            assert int(counters.abs().sum()) == 0 and int(csum.abs().sum()) == 0, mode
+        C.set_slab_reduce_mode(0)
+        G, dst, tags = put(11, corrupt=True)
+        assert torch.equal(G, want) and C.verify_rows(dst, tags, 11, 3)
+    finally:
+        C.set_slab_reduce_mode(1)
+        flags.close()
 
 
 @pytest.mark.parametrize("d,sizes", [(1000, [3000, 2000, 1000]), (1000, [37, 5, 70]), (504, [900, 33, 64]),
