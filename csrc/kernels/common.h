@@ -360,7 +360,7 @@ __device__ __forceinline__ double loss_value(double y, double p) {
 
 __host__ __device__ constexpr int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-// Stale-round gate of a lazy-drain worker round (launchers.h PutDesc::gate, engine.cpp WorkerPump):
+// Stale-round gate of a lazy-drain worker round (launchers.h PutDesc::gate, worker_pump.cpp WorkerPump):
 // nonzero = the master had published the next beta before this round could start, so every kernel
 // of the round returns at once.  The value is launch-uniform (written by the previous round's put
 // kernel, stream-ordered before this launch), so whole grids return together and no barrier is left

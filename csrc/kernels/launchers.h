@@ -1,7 +1,7 @@
 // Host-side launch interface of every gfx950 kernel in csrc/kernels/*.hip.
 //
 // Shared by the Python bindings (csrc/bindings.cpp), the IPC runtime (csrc/runtime/ipc.cpp)
-// and the native round executors (csrc/runtime/engine.cpp).  Every launcher enqueues on
+// and the native round executors (csrc/runtime/master_pump.cpp, worker_pump.cpp).  Every launcher enqueues on
 // the given HIP stream and returns the launch error; shapes are validated by the callers.
 #pragma once
 
@@ -216,7 +216,7 @@ struct PutDesc {
   // Abort word (host-mapped, nullptr = none): once non-zero, the put and its signal are skipped
   // (a pump that gave up releases its queued stream waits without announcing stale rounds).
   const int* abort;
-  // Stale-round gate of a lazy-drain worker round (engine.cpp WorkerPump::set_skip_stale; nullptr =
+  // Stale-round gate of a lazy-drain worker round (worker_pump.cpp WorkerPump::set_skip_stale; nullptr =
   // off).  gate: this round's word (common.h gate_closed): nonzero = the round was skipped, nothing
   // is put or announced.  next_gate: the next round's word, decided by this launch once (after the
   // signal, or at once when skipped): 1 iff the worker's beta counter (beta_flag, its device address)

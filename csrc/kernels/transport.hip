@@ -93,7 +93,7 @@ __global__ void signal_only(unsigned long long* flag, unsigned long long value) 
   __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// Stale-round gate of a p2p worker round (engine.cpp WorkerPump::set_skip_stale_comm): the worker's
+// Stale-round gate of a p2p worker round (worker_pump.cpp WorkerPump::set_skip_stale_comm): the worker's
 // beta counter (bumped behind every beta receive on its beta stream) against `at_least`, snapshotted
 // into the round's gate word so every kernel of the round reads one launch-uniform value.
 __global__ void gate_from_counter(const unsigned long long* counter, unsigned long long at_least, int* gate) {

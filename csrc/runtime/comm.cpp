@@ -25,19 +25,17 @@
 #include <vector>
 
 #include "kernels/launchers.h"
+#include "runtime/host_util.h"
 
 namespace {
 namespace py = pybind11;
 using at::Tensor;
+using eh::hcheck;
+using eh::need;
+using eh::put_blocks;
 
-void hcheck(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
 void ncheck(ncclResult_t r, const char* what) {
   if (r != ncclSuccess) throw std::runtime_error(std::string(what) + ": " + ncclGetErrorString(r));
-}
-void need(bool ok, const std::string& msg) {
-  if (!ok) throw std::invalid_argument(msg);
 }
 
 py::bytes nccl_unique_id() {
@@ -175,8 +173,7 @@ class LoopbackComm : public eh::P2PComm {
     eh::PutArgs a{};
     a.n = 1;
     a.d[0] = eh::PutDesc{src, dst, bytes, flag, v, counter};
-    const int blocks = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(64, (bytes / 16 + 4095) / 4096)));
-    hcheck(eh::put_signal_launch(a, blocks, st), "put_signal(loopback)");
+    hcheck(eh::put_signal_launch(a, put_blocks(bytes), st), "put_signal(loopback)");
   }
   int device_;
   Tensor counters_;
@@ -200,11 +197,9 @@ class RcclSelfLoop {
     hcheck(hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, device), "hipDeviceGetAttribute");
     need(can != 0, "RcclSelfLoop needs hipStreamWaitValue64");
     const int nch = 2 * (world - 1);
-    hcheck(hipHostMalloc(reinterpret_cast<void**>(&flags_h_), sizeof(uint64_t) * 2 * nch,
-                         hipHostMallocMapped | hipHostMallocCoherent),
-           "hipHostMalloc(flags)");
-    std::memset(flags_h_, 0, sizeof(uint64_t) * 2 * nch);
-    hcheck(hipHostGetDevicePointer(reinterpret_cast<void**>(&flags_d_), flags_h_, 0), "hipHostGetDevicePointer");
+    flags_ = std::make_unique<eh::HostMapped>(sizeof(uint64_t) * 2 * nch);
+    auto* fh = static_cast<uint64_t*>(flags_->host);
+    auto* fd = static_cast<uint64_t*>(flags_->dev);
     counters_ = at::zeros({nch}, at::TensorOptions().dtype(at::kInt).device(at::Device(at::kCUDA, device)));
     rings_ = at::zeros({static_cast<int64_t>(nch) * depth * cap}, at::TensorOptions().dtype(at::kByte).device(
                                                                      at::Device(at::kCUDA, device)));
@@ -215,10 +210,10 @@ class RcclSelfLoop {
       Chan& c = chans_[k];
       ncheck(ncclCommInitRank(&c.comm, 1, id, 0), "ncclCommInitRank(1 rank)");
       c.ring = static_cast<char*>(rings_.data_ptr()) + static_cast<int64_t>(k) * depth * cap;
-      c.ready_h = flags_h_ + 2 * k;
-      c.consumed_h = flags_h_ + 2 * k + 1;
-      c.ready_d = reinterpret_cast<unsigned long long*>(flags_d_ + 2 * k);
-      c.consumed_d = reinterpret_cast<unsigned long long*>(flags_d_ + 2 * k + 1);
+      c.ready_h = fh + 2 * k;
+      c.consumed_h = fh + 2 * k + 1;
+      c.ready_d = reinterpret_cast<unsigned long long*>(fd + 2 * k);
+      c.consumed_d = reinterpret_cast<unsigned long long*>(fd + 2 * k + 1);
       c.counter = reinterpret_cast<unsigned int*>(counters_.data_ptr<int>()) + k;
     }
   }
@@ -226,7 +221,6 @@ class RcclSelfLoop {
     hipDeviceSynchronize();
     for (auto& c : chans_)
       if (c.comm) aborted_ ? ncclCommAbort(c.comm) : ncclCommDestroy(c.comm);
-    if (flags_h_) hipHostFree(flags_h_);
   }
   // from -> to, called by the sending thread on its stream
   void send(int from, int to, const void* buf, int64_t bytes, hipStream_t st) {
@@ -250,8 +244,7 @@ class RcclSelfLoop {
     eh::PutArgs a{};
     a.n = 1;
     a.d[0] = eh::PutDesc{c.ring + static_cast<int64_t>(s % depth_) * cap_, buf, bytes, c.consumed_d, s, c.counter};
-    const int blocks = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(64, (bytes / 16 + 4095) / 4096)));
-    hcheck(eh::put_signal_launch(a, blocks, st), "put_signal(self-loop recv)");
+    hcheck(eh::put_signal_launch(a, put_blocks(bytes), st), "put_signal(self-loop recv)");
   }
   void abort() {  // release every queued wait (data after it is garbage)
     aborted_ = true;
@@ -284,8 +277,7 @@ class RcclSelfLoop {
   }
   int device_, world_, depth_;
   int64_t cap_;
-  uint64_t* flags_h_ = nullptr;
-  uint64_t* flags_d_ = nullptr;
+  std::unique_ptr<eh::HostMapped> flags_;  // ready / consumed counters of every channel
   Tensor counters_, rings_;
   std::vector<Chan> chans_;
   bool aborted_ = false;
@@ -308,8 +300,6 @@ class RcclSelfView : public eh::P2PComm {
   int me_;
 };
 
-hipStream_t cur_stream(const Tensor& t) { return c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
-
 }  // namespace
 
 namespace eh {
@@ -318,11 +308,11 @@ void bind_comm(py::module& m) {
   py::class_<P2PComm, std::shared_ptr<P2PComm>>(m, "P2PComm")
       .def("send", [](P2PComm& c, int peer, const Tensor& t) {
         need(t.is_cuda() && t.is_contiguous(), "send: contiguous GPU tensor");
-        c.send(peer, t.data_ptr(), t.numel() * t.element_size(), cur_stream(t));
+        c.send(peer, t.data_ptr(), t.numel() * t.element_size(), eh::stream_of(t));
       })
       .def("recv", [](P2PComm& c, int peer, const Tensor& t) {
         need(t.is_cuda() && t.is_contiguous(), "recv: contiguous GPU tensor");
-        c.recv(peer, t.data_ptr(), t.numel() * t.element_size(), cur_stream(t));
+        c.recv(peer, t.data_ptr(), t.numel() * t.element_size(), eh::stream_of(t));
       })
       .def("abort", &P2PComm::abort)
       .def_property_readonly("kind", &P2PComm::kind);

@@ -1,5 +1,5 @@
 // Stream-ordered point-to-point messaging between the master and the worker ranks, for the
-// native round executors (engine.cpp) when the IPC mailbox cannot be used (several nodes, or
+// native round executors (master_pump.cpp, worker_pump.cpp) when the IPC mailbox cannot be used (several nodes, or
 // GPUs without peer access) — SURVEY §5.8 "RCCL p2p over a dedicated 2-rank communicator per
 // (master, worker) pair".
 //

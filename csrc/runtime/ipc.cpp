@@ -21,27 +21,20 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
-#if defined(__x86_64__)
-#include <immintrin.h>
-#endif
-
 #include "kernels/launchers.h"
+#include "runtime/host_util.h"
 
 namespace {
 namespace py = pybind11;
 using at::Tensor;
-
-void hcheck(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
+using eh::hcheck;
+using eh::put_blocks;
 
 at::ScalarType dtype_of(const std::string& s) {
   if (s == "float64") return at::kDouble;
@@ -188,19 +181,7 @@ class ShmFlags {
   // Spin (then back off) until flag[i] >= v; false on timeout.  GIL released by the binding.
   bool wait_ge(int64_t i, uint64_t v, double timeout) const {
     check(i);
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
-    for (int spin = 0;; ++spin) {
-      if (__atomic_load_n(host_ + i, __ATOMIC_ACQUIRE) >= v) return true;
-      if (spin < 20000) {
-#if defined(__x86_64__)
-        _mm_pause();
-#endif
-        continue;
-      }
-      if (std::chrono::duration<double>(clk::now() - t0).count() > timeout) return false;
-      std::this_thread::sleep_for(std::chrono::microseconds(20));
-    }
+    return eh::wait_until([&] { return __atomic_load_n(host_ + i, __ATOMIC_ACQUIRE) >= v; }, timeout, 20000, 20) >= 0.0;
   }
   int64_t size() const { return n_; }
 
@@ -241,11 +222,8 @@ void put_signal(const std::vector<std::tuple<Tensor, Tensor, uintptr_t, uint64_t
                          reinterpret_cast<unsigned int*>(counters.data_ptr<int>()) + k};
     maxb = std::max(maxb, nb);
   }
-  if (blocks <= 0) blocks = std::max<int64_t>(1, std::min<int64_t>(64, (maxb / 16 + 4095) / 4096));
-  const auto& src0 = std::get<0>(puts[0]);
-  hcheck(eh::put_signal_launch(a, static_cast<int>(blocks),
-                               c10::hip::getCurrentHIPStream(src0.device().index()).stream()),
-         "put_signal");
+  if (blocks <= 0) blocks = put_blocks(maxb);
+  hcheck(eh::put_signal_launch(a, static_cast<int>(blocks), eh::stream_of(std::get<0>(puts[0]))), "put_signal");
 }
 
 // One gated put (launchers.h PutDesc::gate, the lazy-drain stale-round gate) of src into dst with its
@@ -268,9 +246,7 @@ void put_signal_gated(const Tensor& src, const Tensor& dst, uintptr_t flag, uint
   d.next_gate = gate.data_ptr<int>() + 1;
   d.beta_flag = reinterpret_cast<const unsigned long long*>(beta_flag);
   d.stale_next = stale_next;
-  const int blocks = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(64, (nb / 16 + 4095) / 4096)));
-  hcheck(eh::put_signal_launch(a, blocks, c10::hip::getCurrentHIPStream(src.device().index()).stream()),
-         "put_signal_gated");
+  hcheck(eh::put_signal_launch(a, put_blocks(nb), eh::stream_of(src)), "put_signal_gated");
 }
 
 // One tagged put (csrc/kernels/integrity.h) of src [rows, ld] into dst, with one MsgTag per row into
@@ -299,30 +275,22 @@ void put_signal_tagged(const Tensor& src, const Tensor& dst, const Tensor& tags,
   d.es = static_cast<int>(es);
   d.rank = static_cast<unsigned int>(rank);
   d.corrupt = corrupt ? 1 : 0;
-  const int64_t nb = src.numel() * es;
-  const int blocks = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(64, (nb / 16 + 4095) / 4096)));
-  hcheck(eh::put_signal_launch(a, blocks, c10::hip::getCurrentHIPStream(src.device().index()).stream()),
-         "put_signal_tagged");
+  hcheck(eh::put_signal_launch(a, put_blocks(src.numel() * es), eh::stream_of(src)), "put_signal_tagged");
 }
 
 // Check the rows [n, ld] of one put against tags (uint8 [n * 16]) for counter value round1 and sender
 // `rank`; returns the first failure as a dict (empty when every row matches).  Synchronises.
 py::dict verify_rows(const Tensor& rows, const Tensor& tags, int64_t round1, int64_t rank) {
   if (!rows.is_cuda() || !tags.is_cuda() || rows.dim() != 2) throw std::invalid_argument("verify_rows: GPU [n, ld]");
-  void* h = nullptr;
-  void* dptr = nullptr;
-  hcheck(hipHostMalloc(&h, sizeof(eh::IntegrityErr), hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc");
-  std::memset(h, 0, sizeof(eh::IntegrityErr));
-  hcheck(hipHostGetDevicePointer(&dptr, h, 0), "hipHostGetDevicePointer");
-  const hipStream_t st = c10::hip::getCurrentHIPStream(rows.device().index()).stream();
+  eh::HostMapped err(sizeof(eh::IntegrityErr));
+  const hipStream_t st = eh::stream_of(rows);
   hipError_t e = eh::verify_rows_launch(rows.data_ptr(), static_cast<const eh::MsgTag*>(tags.data_ptr()),
                                         static_cast<int>(rows.size(0)), static_cast<int>(rows.size(1)),
                                         static_cast<int>(rows.element_size()), static_cast<unsigned int>(round1),
-                                        static_cast<unsigned int>(rank), static_cast<eh::IntegrityErr*>(dptr), 0, st);
+                                        static_cast<unsigned int>(rank), static_cast<eh::IntegrityErr*>(err.dev), 0, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  const eh::IntegrityErr r = *static_cast<eh::IntegrityErr*>(h);
-  hipHostFree(h);
   hcheck(e, "verify_rows");
+  const eh::IntegrityErr r = *static_cast<eh::IntegrityErr*>(err.host);
   py::dict out;
   if (r.flag) {
     out["round"] = r.round;

@@ -26,9 +26,9 @@ import numpy as np
 
 from .cyclic import DecodeCache, make_cyclic_B
 
-# stop-rule kinds (must match csrc/runtime/collector.h)
+# stop-rule kinds (csrc/runtime/collector.h RuleKind; tests/test_native_enums.py compares the two)
 RULE_ALL, RULE_COUNT, RULE_FRC, RULE_PARTIAL_FRC, RULE_PARTIAL_COUNT = range(5)
-# host decode kinds of the native master executor (must match csrc/runtime/engine.cpp DecodeKind)
+# host decode kinds of the native master executor (csrc/runtime/decode.h DecodeKind; same test)
 DEC_SUM, DEC_FIRST_PER_GROUP, DEC_PARTIAL_FRC, DEC_TABLE, DEC_PARTIAL_TABLE = range(5)
 
 

@@ -78,7 +78,7 @@ class RunConfig:
     trace: bool = False
     tasks: int = 0  # override gradient-kernel workgroup count
     verify_beta: bool = False  # race detector: workers checksum beta before/after use (Python loop)
-    native_loop: bool = True  # GPU rounds in the C++ executors (csrc/runtime/engine.cpp)
+    native_loop: bool = True  # GPU rounds in the C++ executors (csrc/runtime/master_pump.cpp, worker_pump.cpp)
     sync_update: bool = False  # host waits for every round's update kernel (else timed by HIP events)
     transport: str = "auto"  # auto | ipc | rccl | gloo (parallel/transport.py)
     device_loop: str = "auto"  # auto|graph|stream|off: device-driven rounds when eligible (trainer._device_loop_mode)

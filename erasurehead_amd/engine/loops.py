@@ -8,7 +8,7 @@ five executors, picked per run from the configuration:
   master loop   where the master's per-round work runs
   ------------  -----------------------------------------------------------------------------
   python        engine/trainer.py _master_loop: the CPU / gloo path and the race-check path
-  native pump   csrc/runtime/engine.cpp MasterPump::begin/finish: the host collector polls HIP
+  native pump   csrc/runtime/master_pump.cpp MasterPump::begin/finish: the host collector polls HIP
                 events / IPC counters, decodes on the host, launches combine + update
   arbiter       MasterPump::run_device: csrc/kernels/arbiter.hip polls the workers' counters,
                 decodes, updates and releases the next beta on the device (multi-GPU, IPC)

@@ -787,7 +787,7 @@ class Trainer:
         return inner.choice.label()
 
     def _master_loop_native(self, timed_start, log, start: int = 0) -> TrainResult:
-        """Master rounds in csrc/runtime/engine.cpp (MasterPump); Python only keeps the books."""
+        """Master rounds in csrc/runtime/master_pump.cpp (MasterPump); Python only keeps the books."""
         cfg, env, sch = self.cfg, self.env, self.scheme
         R, W, K = cfg.num_itrs, cfg.n_workers, self.K
         C = native_ext()
@@ -1016,7 +1016,7 @@ class Trainer:
         return mode == "device" or (mode == "auto" and not cls._shared_gpu(tx))
 
     def _worker_loop_native(self, timed_start, start: int = 0) -> None:
-        """Worker rounds in csrc/runtime/engine.cpp (WorkerPump) over the IPC mailbox."""
+        """Worker rounds in csrc/runtime/worker_pump.cpp (WorkerPump) over the IPC mailbox."""
         cfg, env, tx = self.cfg, self.env, self.tx
         R, K = cfg.num_itrs, self.K
         C = native_ext()

@@ -459,6 +459,7 @@ class DenseGradPlan:
             target_tasks = REPLICA_TASKS if c.interleave else DEFAULT_TASKS
         if self.bundle_rows:
             target_tasks = max(1, -(-self.total_rows // self.bundle_rows))
+        self._run_launcher = None  # run()'s own launcher (native_launcher() hands out fresh ones)
         if self.device.type == "cuda":
             self._native_choice = c.native()
             self._build_tables(target_tasks)
@@ -574,18 +575,14 @@ class DenseGradPlan:
         if G.shape != (self.nslots, self.ld):
             raise ValueError(f"G must be [{self.nslots}, {self.ld}]")
         if self.device.type == "cuda":
-            C = native()
-            if self.cpl is not None:
-                C.grad_dense(self.prec.code, self.loss, self.cpl, self.segs, self.tasks, beta, self.slab,
-                             self.slot_task_begin, self.part, G, self.ld, self._native_choice)
-            else:
-                C.grad_dense_twopass(self.prec.code, self.loss, self.segs, self.tasks, beta, self.task_row_off,
-                                     self.rbuf, self.slab, self.slot_task_begin, self.part, G, self.ld)
+            if self._run_launcher is None:
+                self._run_launcher = self.native_launcher()
+            self._run_launcher.launch(beta, G)
             return G
         return self._run_torch(beta, G)
 
     def native_launcher(self):
-        """C++ GradLauncher for the native round executors (csrc/runtime/engine.cpp)."""
+        """A NEW C++ GradLauncher (csrc/runtime/grad_launcher.h): SharedGradPlan.native_launcher extends it."""
         if self.device.type != "cuda":
             raise RuntimeError("native launchers need GPU tensors")
         C = native()

@@ -135,7 +135,7 @@ class SoftmaxGradPlan:
         return torch.zeros((n, self.nslots, self.ld), dtype=self.prec.acc, device=self.device)
 
     def native_launcher(self):
-        """C++ GradLauncher for the native round executors (csrc/runtime/engine.cpp)."""
+        """C++ GradLauncher (csrc/runtime/grad_launcher.h) for the native round executors."""
         if self.device.type != "cuda":
             raise RuntimeError("native launchers need GPU tensors")
         if self._launcher is None:
@@ -151,12 +151,7 @@ class SoftmaxGradPlan:
         if G.shape != (self.nslots, self.ld):
             raise ValueError(f"G must be [{self.nslots}, {self.ld}]")
         if self.device.type == "cuda":
-            C = native()
-            out = G if self.identity else self.Gb
-            C.grad_softmax(self.prec.code, self.classes, self.segs, self.tasks, self.part_task_begin, beta, self.slab,
-                           out, self.d_x, self.ld_x)
-            if not self.identity:
-                C.encode_messages(self.Gb, self.enc_ptr, self.enc_idx, self.enc_coef, G)
+            self.native_launcher().launch(beta, G)  # the gradient into Gb, then encode_messages (identity: into G)
             return G
         acc = self.prec.acc
         B = beta.to(acc).reshape(self.classes, self.ld_x)

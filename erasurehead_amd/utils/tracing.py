@@ -18,7 +18,7 @@ _ENABLED = os.environ.get("ERASUREHEAD_TRACE", "0") not in ("0", "", "false")
 
 def enable(flag: bool = True) -> None:
     """Turn roctx ranges on for the Python engine and (via the environment, read once) the
-    native executors in csrc/runtime/engine.cpp."""
+    native executors in csrc/runtime/master_pump.cpp and worker_pump.cpp."""
     global _ENABLED
     _ENABLED = flag
     if flag:

@@ -2,7 +2,7 @@
 ranks' own device records -- no model of host or GPU scheduling.
 
 Every physically late worker rank records, on its GPU clock (Trainer device_records, csrc/runtime/
-engine.cpp WorkerPump::set_records), when each round's put landed (the stamp its put kernel writes just
+worker_pump.cpp WorkerPump::set_records), when each round's put landed (the stamp its put kernel writes just
 before the flag), its spin, and the brackets around its stale-round decisions; the master records the
 brackets around every beta put and its collector's probe log (each message's seen time, which for a
 physically late rank IS its landing time: collector.h "Device times", and what became of it).  The

@@ -111,7 +111,8 @@ def test_rounds_must_increase(C):
 
 
 def test_collector_host_asan_ubsan():
-    """The collector state machine under AddressSanitizer + UBSan (host build, tools/sanitize_host.sh)."""
+    """The collector state machine and the master's decode (csrc/runtime/decode.h) under AddressSanitizer +
+    UBSan (host builds, tools/sanitize_host.sh)."""
     import shutil
     import subprocess
 
@@ -122,6 +123,7 @@ def test_collector_host_asan_ubsan():
                        timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "collector selftest ok" in r.stdout
+    assert "decode selftest ok" in r.stdout
 
 
 def test_wait_seen_ignores_virtual_delay(C):

@@ -1,0 +1,82 @@
+"""GradLauncher.launch checks its operands on the host (csrc/runtime/grad_launcher.h check_operands): a G with
+too few rows, a G or beta of the wrong dtype and a beta shorter than ld raise before anything is enqueued, for a
+dense, a softmax and a sparse plan; GradLauncher.dense rejects a dtype code outside 0..2 (GPU only)."""
+import numpy as np
+import pytest
+import scipy.sparse as sps
+import torch
+
+from erasurehead_amd.models.losses import SQUARED_HINGE
+from erasurehead_amd.ops import DenseGradPlan, SparseGradPlan, get_precision
+from erasurehead_amd.ops.softmax import SoftmaxGradPlan
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+PREC = get_precision("fp64")
+D = 37
+SIZES = [64, 33]  # two partitions, one message
+
+
+def _dense_parts(rng, labels):
+    parts = {}
+    for p, n in enumerate(SIZES):
+        X = torch.zeros((n, PREC.ld(D)), dtype=torch.float64)
+        X[:, :D] = torch.from_numpy(rng.randn(n, D) * 0.3)
+        parts[p] = (X.to(DEV).contiguous(), torch.from_numpy(labels(n)).to(DEV))
+    return parts
+
+
+def _dense_plan(rng):
+    parts = _dense_parts(rng, lambda n: rng.choice([-1.0, 1.0], n))
+    return DenseGradPlan([[(0, 1.0), (1, 1.0)]], parts, PREC, SQUARED_HINGE, D)
+
+
+def _softmax_plan(rng):
+    parts = _dense_parts(rng, lambda n: rng.randint(0, 3, n).astype(np.float64))
+    return SoftmaxGradPlan([[(0, 1.0), (1, 1.0)]], parts, PREC, 3, D)
+
+
+def _sparse_plan(rng):
+    parts = {}
+    for p, n in enumerate(SIZES):
+        cols = np.stack([rng.choice(D, 5, replace=False) for _ in range(n)])
+        X = sps.csr_matrix((rng.randn(cols.size), cols.ravel(), np.arange(0, cols.size + 1, 5)), shape=(n, D))
+        parts[p] = (X, rng.choice([-1.0, 1.0], n))
+    return SparseGradPlan([[(0, 1.0), (1, 0.5)]], parts, PREC, SQUARED_HINGE, D, device=DEV)
+
+
+@pytest.mark.parametrize("make", [_dense_plan, _softmax_plan, _sparse_plan], ids=["dense", "softmax", "sparse"])
+def test_launch_rejects_bad_operands_and_computes_nothing(make, native):
+    rng = np.random.RandomState(1)
+    plan = make(rng)
+    assert plan.nslots == 1
+    L = plan.native_launcher()
+    beta = torch.from_numpy(rng.randn(plan.ld) * 0.5).to(DEV)
+    G = torch.full((plan.nslots, plan.ld), 123.0, dtype=PREC.acc, device=DEV)
+    bad = {
+        "G with one row too few": (beta, G[: plan.nslots - 1]),
+        "G in fp32": (beta, torch.full((plan.nslots, plan.ld), 123.0, dtype=torch.float32, device=DEV)),
+        "beta with ld - 1 elements": (beta[: plan.ld - 1].contiguous(), G),
+    }
+    for what, (b, g) in bad.items():
+        with pytest.raises(ValueError):
+            L.launch(b, g)
+        torch.cuda.synchronize()
+        assert torch.all(g == 123.0) and torch.all(G == 123.0), what
+    L.launch(beta, G)  # the same launcher with correct operands
+    torch.cuda.synchronize()
+    assert not torch.any(G.reshape(-1, PREC.ld(D))[:, :D] == 123.0)  # every data column (of every class block)
+
+
+def test_dense_plan_rejects_unknown_dtype_code(native):
+    rng = np.random.RandomState(1)
+    plan = _dense_plan(rng)
+    G = torch.full((plan.nslots, plan.ld), 123.0, dtype=PREC.acc, device=DEV)
+    with pytest.raises(ValueError):
+        native.GradLauncher.dense(5, SQUARED_HINGE, plan.cpl, plan.segs, plan.tasks, plan.slab, plan.slot_task_begin,
+                                  plan.part, plan.ld, choice=plan._native_choice)
+    torch.cuda.synchronize()
+    assert torch.all(G == 123.0)
+    plan.native_launcher().launch(torch.ones(plan.ld, dtype=PREC.acc, device=DEV), G)
+    torch.cuda.synchronize()
+    assert not torch.any(G[:, :D] == 123.0)

@@ -402,8 +402,8 @@ def test_unknown_loss_code_raises_and_computes_nothing(native):
     beta, _ = _beta(rng, d, prec)
     G = torch.full((plan.nslots, plan.ld), 123.0, dtype=prec.acc, device=DEV)
     with pytest.raises(RuntimeError):
-        native.grad_dense(prec.code, 7, plan.cpl, plan.segs, plan.tasks, beta, plan.slab, plan.slot_task_begin,
-                          plan.part, G, plan.ld, plan._native_choice)
+        native.GradLauncher.dense(prec.code, 7, plan.cpl, plan.segs, plan.tasks, plan.slab, plan.slot_task_begin,
+                                  plan.part, plan.ld, choice=plan._native_choice).launch(beta, G)
     torch.cuda.synchronize()
     assert torch.all(G == 123.0)
     plan.run(beta, G)  # the same operands with a known code
