@@ -435,8 +435,10 @@ class DenseGradPlan:
                 raise ValueError(f"partition {p}: y must be [{X.shape[0]}] {prec.acc}")
         self.total_rows = sum(partitions[p][0].shape[0] for m in self.messages for p, _ in m)
         self.cpl = choose_cpl(self.ld, prec.vec)
-        # co-located replicas: a partition read by several local messages
-        self.max_rep = max(collections.Counter(p for m in self.messages for p, _ in m).values(), default=0)
+        # co-located replicas: a partition read by several local messages (an empty partition has no rows
+        # to share: counting it would pick a replica kernel for bundles that hold fewer replicas)
+        self.max_rep = max(collections.Counter(p for m in self.messages for p, _ in m
+                                               if partitions[p][0].shape[0] > 0).values(), default=0)
         part_rows = [partitions[p][0].shape[0] for p in sorted({p for m in self.messages for p, _ in m})]
         distinct_rows = sum(part_rows)
         self.choice = choice or choose_kernel(prec.code, self.ld, self.cpl, self.max_rep, distinct_rows,
@@ -481,7 +483,8 @@ class DenseGradPlan:
                 X, y = self.partitions[p]
                 n = X.shape[0]
                 segs += _SEG.pack(X.data_ptr(), y.data_ptr(), float(coef), n)
-                bounds = splits[p] if splits else list(range(0, n, rows_per_task)) + [n]
+                # (fill_splits leaves out empty partitions: they get no task)
+                bounds = splits.get(p, [0]) if splits else list(range(0, n, rows_per_task)) + [n]
                 for r0, r1 in zip(bounds[:-1], bounds[1:]):
                     tasks.append((slot, seg_id, r0, r1, len(tasks)))
                     keys.append((p, r0))
@@ -519,6 +522,8 @@ class DenseGradPlan:
         groups: List[List[int]] = []
         for b in bundles.values():
             groups += [b[i:i + MAX_BUNDLE] for i in range(0, len(b), MAX_BUNDLE)]
+        if not groups:
+            raise ValueError("every partition of the plan's messages is empty: there is no row to bundle")
         R = max(len(g) for g in groups)
         if R != self.choice.replicas:
             raise ValueError(f"the plan's bundles hold {R} replicas, the kernel choice {self.choice.replicas}")

@@ -1,0 +1,160 @@
+"""Hostile inputs, a long-double oracle and per-column forward-error bounds for the dense kernels.
+
+The older GPU tests draw ``X ~ 0.3 N(0, 1)`` with i.i.d. columns and divide the error by the largest
+gradient entry; a column whose gradient is 1e-4 of the largest can then be entirely wrong and pass.
+Here the columns of X span four decades of scale, about 5 % of the entries are exact zeros, beta is
+scaled so that a large share of the rows saturate (|z| > 30), and every column of a result is held
+to its own bound
+
+    bound_j = K u sum_p sum_i (|r_i| + L_p sum_k |x_ik beta_k|) |x_ij|  +  tiny sum_p |c_p| sum_i |x_ij|
+
+with u the accumulator's epsilon (2^-52 fp64, 2^-23 fp32 accumulation of fp32 / bf16 storage), tiny
+its smallest normal (a hardware exp2 may flush a denormal sigmoid to zero) and L_p the Lipschitz
+constant of the residual in z (|c_p| / 4 logistic, 2 |c_p| least squares and squared hinge).  The
+first term is the accumulation error of X^T r, the second the dot product's error carried through
+the residual.
+
+K is measured, not chosen: the largest ``err_j / (u sum ...)`` the plain same-precision torch path
+(``DenseGradPlan._run_torch`` on CPU tensors) reaches over the grid of tests/test_numerics_cpu.py
+(d in {37, 1000, 4097}, n in {1, 65, 257}, three losses, three precisions) is
+
+    MEASURED_CPU_RATIO = 0.72   (0.712: fp64, least squares, d = 37, n = 257; fp32 / bf16 stay below 0.46)
+
+and K = 8 x that, rounded up to a power of two = 8.  The factor 8: the kernels sum lane-strided and
+then by tree, not in BLAS order.  K stays orders of magnitude below the worst case (n + d) u.  A
+kernel that needs a larger K is a finding to explain, not a reason to raise it; no kernel family has
+a K of its own.
+
+The evaluation GEMM uses the same scheme: |dP_ij| <= K u sum_k |x_ik b_jk|, and for the loss sums
+sum_i Lip_i dP_ij + K 2^-52 sum_i loss_i (Lip_i = 1 logistic, 2 |y - p| least squares,
+2 max(0, 1 - y p) squared hinge; the epilogue sums in fp64 with atomics).
+
+The oracle computes in ``np.longdouble`` with scipy's overflow-free expit and shares no code with
+erasurehead_amd.models.losses (only the integer loss codes are the package's).
+"""
+import numpy as np
+import torch
+from scipy.special import expit
+
+LOGISTIC, LEAST_SQUARES, SQUARED_HINGE = 0, 1, 2
+LOSSES = (LOGISTIC, LEAST_SQUARES, SQUARED_HINGE)
+LOSS_IDS = {LOGISTIC: "logistic", LEAST_SQUARES: "lsq", SQUARED_HINGE: "sqhinge"}
+
+MEASURED_CPU_RATIO = 0.72
+K = 8  # 8 x MEASURED_CPU_RATIO, rounded up to a power of two
+
+LD = np.longdouble
+SATURATED = 30.0  # |z| beyond which a row counts as saturated
+
+
+def acc_eps(prec) -> float:
+    """Epsilon of the accumulator type."""
+    return 2.0 ** -52 if prec.acc == torch.float64 else 2.0 ** -23
+
+
+def acc_tiny(prec) -> float:
+    """Smallest normal of the accumulator type."""
+    return float(np.finfo(np.float64 if prec.acc == torch.float64 else np.float32).tiny)
+
+
+def hostile_partition(rng, n, d, prec):
+    """(X [n, ld] storage dtype, y [n] accumulator dtype, fp64 view [n, d] of the stored values).
+
+    N(0, 1) entries scaled per column by 10**U(-3, 1), about 5 % exact zeros, labels +-1, padding
+    columns d..ld exactly zero (the engine's contract).  n = 0 gives [0, ld] tensors."""
+    scale = 10.0 ** rng.uniform(-3.0, 1.0, d)
+    X = rng.randn(n, d) * scale
+    X[rng.uniform(size=(n, d)) < 0.05] = 0.0
+    y = rng.choice([-1.0, 1.0], n)
+    Xp = torch.zeros((n, prec.ld(d)), dtype=torch.float64)
+    Xp[:, :d] = torch.from_numpy(X)
+    Xs = Xp.to(prec.storage).contiguous()
+    return Xs, torch.from_numpy(y).to(prec.acc), Xs[:, :d].double().numpy()
+
+
+def hostile_beta(rng, d, prec):
+    """(beta [ld] accumulator dtype, its fp64 view [d]): randn(d) 10**U(-2, 0.5, d) 30 / sqrt(d), zero
+    padding; with hostile_partition's rows a large share of the margins saturate."""
+    b = rng.randn(d) * 10.0 ** rng.uniform(-2.0, 0.5, d) * 30.0 / np.sqrt(d)
+    beta = torch.zeros(prec.ld(d), dtype=prec.acc)
+    beta[:d] = torch.from_numpy(b).to(prec.acc)
+    return beta, beta[:d].double().numpy()
+
+
+def lipschitz(loss, coef):
+    """Lipschitz constant of the residual in z."""
+    return abs(coef) / 4.0 if loss == LOGISTIC else 2.0 * abs(coef)
+
+
+def oracle_residual(loss, z, y, coef):
+    """r_i in long double: the derivative of coef * loss(y_i, z_i) in z_i."""
+    z, y, c = np.asarray(z, LD), np.asarray(y, LD), LD(coef)
+    if loss == LOGISTIC:
+        return -(c * y) * expit(-(y * z))
+    if loss == LEAST_SQUARES:
+        return -2 * c * (y - z)
+    if loss == SQUARED_HINGE:
+        return -2 * c * y * np.maximum(LD(0), 1 - y * z)
+    raise ValueError(f"unknown loss {loss}")
+
+
+def oracle_segment(loss, Xh, yh, bh, coef):
+    """One segment: (gradient [d], K-free bound sum [d], sum_i |x_ij| [d], z [n]) in long double."""
+    X, b = np.asarray(Xh, LD), np.asarray(bh, LD)
+    z = X @ b
+    r = oracle_residual(loss, z, yh, coef)
+    aX = np.abs(X)
+    w = np.abs(r) + LD(lipschitz(loss, coef)) * (aX @ np.abs(b))
+    return X.T @ r, aX.T @ w, aX.sum(0), z
+
+
+def oracle_message(loss, segments, host, bh, prec, k=K):
+    """(gradient, per-column bound) of one message; segments = [(partition, coef)], host[p] = (X, y)."""
+    d = len(bh)
+    g, acc, tiny = np.zeros(d, LD), np.zeros(d, LD), np.zeros(d, LD)
+    for p, coef in segments:
+        gs, ws, ax, _ = oracle_segment(loss, host[p][0], host[p][1], bh, coef)
+        g += gs
+        acc += ws
+        tiny += abs(coef) * ax
+    return g, LD(k * acc_eps(prec)) * acc + LD(acc_tiny(prec)) * tiny
+
+
+def column_ratio(got, ref, bound):
+    """Largest |got_j - ref_j| / bound_j over the columns (0 / 0 counts as 0, x / 0 as inf)."""
+    err = np.abs(np.asarray(got, LD) - ref)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(err == 0, LD(0), err / bound)
+    return float(np.max(q)) if q.size else 0.0
+
+
+def check_columns(got, ref, bound, what=""):
+    """Every column within its own bound; the message names the worst column."""
+    assert np.all(np.isfinite(np.asarray(got, np.float64))), f"{what}: non-finite entries (unwritten or overflowed)"
+    err = np.abs(np.asarray(got, LD) - ref)
+    bad = np.nonzero(~(err <= bound))[0]
+    if bad.size:
+        j = bad[np.argmax((err[bad] / np.maximum(bound[bad], np.finfo(LD).tiny)))]
+        raise AssertionError(f"{what}: {bad.size} of {err.size} columns beyond their bound; worst column {j}: "
+                             f"got {float(got[j])!r} ref {float(ref[j])!r} err {float(err[j]):.3e} "
+                             f"bound {float(bound[j]):.3e} (K = {K})")
+
+
+# ---- evaluation GEMM ------------------------------------------------------------------------------
+def oracle_eval(loss, Xh, yh, Bh, prec, k=K):
+    """(P [n, R], bound on P, loss sums [R], bound on the sums) in long double."""
+    X, B, y = np.asarray(Xh, LD), np.asarray(Bh, LD), np.asarray(yh, LD)[:, None]
+    P = X @ B.T
+    dP = LD(k * acc_eps(prec)) * (np.abs(X) @ np.abs(B).T)
+    if loss == LOGISTIC:
+        m = -y * P
+        per = np.maximum(m, 0) + np.log1p(np.exp(-np.abs(m)))
+        lip = np.ones_like(P)
+    elif loss == LEAST_SQUARES:
+        per = (y - P) ** 2
+        lip = 2 * np.abs(y - P)
+    else:
+        h = np.maximum(LD(0), 1 - y * P)
+        per = h * h
+        lip = 2 * h
+    return P, dP, per.sum(0), (lip * dP).sum(0) + LD(k * 2.0 ** -52) * per.sum(0)
