@@ -272,8 +272,9 @@ inline hipError_t dispatch_loss(int loss, F&& f) {
 }
 
 // Runtime storage code (launchers.h dtype) -> compile-time (storage T, accumulator A): 0 double / double,
-// 1 float / float, 2 bf16_t / float.  f is called with a StorageTag and returns a hipError_t; an unknown
-// code launches nothing.
+// 1 float / float, 2 bf16_t / float, 3 float / double (fp32 rows widened at load, everything computed from
+// them in fp64).  f is called with a StorageTag and returns a hipError_t; an unknown code launches nothing.
+// launchers.h storage_acc_code / storage_acc_bytes give the accumulator of a code on the host.
 template <typename T_, typename A_> struct StorageTag { using T = T_; using A = A_; };
 template <typename F>
 inline hipError_t dispatch_storage(int dtype, F&& f) {
@@ -281,6 +282,7 @@ inline hipError_t dispatch_storage(int dtype, F&& f) {
     case 0: return f(StorageTag<double, double>{});
     case 1: return f(StorageTag<float, float>{});
     case 2: return f(StorageTag<bf16_t, float>{});
+    case 3: return f(StorageTag<float, double>{});
     default: return hipErrorInvalidValue;
   }
 }

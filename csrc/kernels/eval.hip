@@ -6,6 +6,7 @@
 // i.e. P = X . B^T  (n x d times d x R) — a real GEMM, so it runs on the matrix cores:
 //   fp64 X : v_mfma_f64_16x16x4_f64   (exact fp64, matches the numpy reference)
 //   fp32 / bf16 X : v_mfma_f32_16x16x4_f32 (exact f32 products, bf16 widened on staging)
+//   fp32 X, fp64 B / y / P (storage code 3): X widened on staging, v_mfma_f64_16x16x4_f64
 // Tiling: 256-thread workgroup = 4 waves = 64 rows x (16*NT) columns of P; K staged
 // through LDS in 32-deep tiles (row stride padded to 34 elements: conflict-free
 // ds_read_b64 for the 16x4 fragment pattern).  The epilogue applies softplus(-y p),
@@ -43,6 +44,7 @@ template <typename T, typename A>
 __device__ __forceinline__ A load_elem(const T* p);
 template <> __device__ __forceinline__ double load_elem<double, double>(const double* p) { return *p; }
 template <> __device__ __forceinline__ float load_elem<float, float>(const float* p) { return *p; }
+template <> __device__ __forceinline__ double load_elem<float, double>(const float* p) { return static_cast<double>(*p); }
 template <> __device__ __forceinline__ float load_elem<bf16_t, float>(const bf16_t* p) { return bf16_to_f32(p->bits); }
 
 constexpr int kKT = 32;   // K tile
@@ -245,7 +247,8 @@ eval_gemm_loss_v2(const T* __restrict__ X, long long ldx, long long n, int d,
   }
 }
 
-// x_dtype: 0 fp64, 1 fp32, 2 bf16.  B/y/P are fp64 for x_dtype 0, fp32 otherwise.
+// x_dtype: the storage code of launchers.h -- 0 fp64, 1 fp32, 2 bf16, 3 fp32 X with fp64 B/y/P.  B/y/P are
+// fp64 for x_dtype 0 and 3, fp32 otherwise.
 hipError_t eval_gemm_loss_launch(int x_dtype, int loss_kind, const void* X, long long ldx,
                                  long long n, int d, const void* y, const void* B, int ldb,
                                  int R, double* loss, void* P, hipStream_t st) {
@@ -254,7 +257,8 @@ hipError_t eval_gemm_loss_launch(int x_dtype, int loss_kind, const void* X, long
   const dim3 grid(static_cast<unsigned>((n + 63) / 64), ceil_div(R, 16 * NT));
   if (n == 0 || R == 0) return hipSuccess;
   // v2 needs 16-byte aligned rows (every tensor the engine builds: ld is a vector multiple)
-  const int xv = x_dtype == 0 ? 2 : (x_dtype == 1 ? 4 : 8), bv = x_dtype == 0 ? 2 : 4;
+  if (x_dtype < 0 || x_dtype > 3) return hipErrorInvalidValue;
+  const int xv = x_dtype == 0 ? 2 : (x_dtype == 2 ? 8 : 4), bv = (x_dtype == 0 || x_dtype == 3) ? 2 : 4;
   const bool aligned = ldx % xv == 0 && ldb % bv == 0 && reinterpret_cast<uintptr_t>(X) % 16 == 0 &&
                        reinterpret_cast<uintptr_t>(B) % 16 == 0;
   if (aligned) {
@@ -265,6 +269,7 @@ hipError_t eval_gemm_loss_launch(int x_dtype, int loss_kind, const void* X, long
       constexpr int kL = decltype(L)::value;
       if (x_dtype == 0) EH_EVAL2(double, double, kL);
       else if (x_dtype == 1) EH_EVAL2(float, float, kL);
+      else if (x_dtype == 3) EH_EVAL2(float, double, kL);
       else EH_EVAL2(bf16_t, float, kL);
       return hipGetLastError();
     });
@@ -276,6 +281,7 @@ hipError_t eval_gemm_loss_launch(int x_dtype, int loss_kind, const void* X, long
     constexpr int kL = decltype(L)::value;
     if (x_dtype == 0) EH_EVAL(double, double, kL);
     else if (x_dtype == 1) EH_EVAL(float, float, kL);
+    else if (x_dtype == 3) EH_EVAL(float, double, kL);
     else EH_EVAL(bf16_t, float, kL);
     return hipGetLastError();
   });

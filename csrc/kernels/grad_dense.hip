@@ -194,8 +194,15 @@ grad_dense_fused(const Segment* __restrict__ segs, const Task* __restrict__ task
 // 1181 us at the N = 1 rank shape, 278 VGPRs), 3 for fp32 (4 KB rows: 570-573 vs 588-590 us at N = 1, 81-83
 // vs 84 at N = 8, profiles/round6/fp32_depth; 4 was slower, round 5), 6 for bf16 (2 KB rows: 12 KB in flight
 // per wave; 3 waves per SIMD at R = 3, 169 VGPRs and 2 waves with 8).
-template <typename T>
-constexpr int kMultiDepth = std::is_same<T, bf16_t>::value ? 6 : std::is_same<T, float>::value ? 3 : 2;
+// The packed-fp32 forms (v_pk_fma_f32 on float2 operands) are for fp32 rows with fp32 accumulators only.
+template <typename T, typename A>
+constexpr bool kPackedF32 = std::is_same<T, float>::value && std::is_same<A, float>::value;
+// fp32 rows with fp64 accumulators (4 KB rows like fp32, beta and the gradient slices of fp64): 2, the only depth
+// that holds three replicas within 256 VGPRs (226; logistic at 3: 257, at 4: 276).  One or two replicas fit at 3
+// and 4 (R = 1: 211 / 229, R = 2: 224 / 242), measured within +-4 % of 2 either way -- faster at 1e6 rows, slower
+// at the 125k-row rank shape (docs/PERF_NOTES.md, fp32x64) -- so the depth does not follow the replica count.
+template <typename T, typename A>
+constexpr int kMultiDepth = std::is_same<T, bf16_t>::value ? 6 : kPackedF32<T, A> ? 3 : 2;
 
 template <typename T, typename A, int CPL, int LOSS, int R, bool FOLD, int EPI = 0>
 __global__ void __launch_bounds__(256)
@@ -362,11 +369,11 @@ grad_dense_multi(const Segment* __restrict__ segs, const Task* __restrict__ task
       load(xb, yb, r + 5);
       step2(xc, xd, yc, yd, r + 3 < r1);
     }
-  } else if constexpr (kMultiDepth<T> > 2) {
+  } else if constexpr (kMultiDepth<T, A> > 2) {
     // Short rows (bf16: 2 KB at d = 1000, two 16-byte vectors per lane): two rows in flight would be 4 KB
     // per wave, too little to cover HBM latency at a CU's share of the stream, so D rows are in flight: a
     // ring of D row buffers, each step issuing the load D - 1 rows ahead before consuming its own row.
-    constexpr int D = kMultiDepth<T>;
+    constexpr int D = kMultiDepth<T, A>;
     Rw xr[D][NV];
     A yr[D];
 #pragma unroll
@@ -539,7 +546,7 @@ grad_dense_staged(const Segment* __restrict__ segs, const Task* __restrict__ tas
           const unsigned char* row0 = buf + i * rowbytes;
           const unsigned char* row1 = two ? row0 + rowbytes : row0;
           A z0 = A(0), z1 = A(0);
-          if constexpr (std::is_same<T, float>::value) {
+          if constexpr (kPackedF32<T, A>) {
             // fp32: both rows' dot products in one packed accumulator {z0, z1} (v_pk_fma_f32)
             typedef float f2 __attribute__((ext_vector_type(2)));
             f2 z01 = f2{0.f, 0.f};
@@ -578,7 +585,7 @@ grad_dense_staged(const Segment* __restrict__ segs, const Task* __restrict__ tas
             const int c0 = min((j * kWave + lane) * VN, ld - VN) * static_cast<int>(sizeof(T));
             const Rw v0 = *reinterpret_cast<const Rw*>(row0 + c0);
             const Rw v1 = *reinterpret_cast<const Rw*>(row1 + c0);
-            if constexpr (std::is_same<T, float>::value) {
+            if constexpr (kPackedF32<T, A>) {
               typedef float f2 __attribute__((ext_vector_type(2)));
               const f2 rr0 = f2{r0, r0}, rr1 = f2{r1, r1};
               f2 lo = __builtin_elementwise_fma(rr0, f2{v0.x, v0.y}, f2{g[j][0], g[j][1]});
@@ -599,7 +606,7 @@ grad_dense_staged(const Segment* __restrict__ segs, const Task* __restrict__ tas
             }
           }
         }
-      } else if constexpr (std::is_same<T, float>::value) {
+      } else if constexpr (kPackedF32<T, A>) {
         // fp32: the same row-at-a-time math on packed v_pk_fma_f32 (two columns per instruction).
         // fp32 rows carry twice the elements per byte of fp64, so the VALU issue rate, not HBM, bound
         // the scalar form (0.83 ms vs 0.73 ms of bytes at the headline); z keeps two partial sums.
@@ -1117,13 +1124,14 @@ static void launch_wide_nv(dim3 grid, hipStream_t st, const Segment* segs, const
   hipLaunchKernelGGL(kern, grid, dim3(BS), 0, st, segs, tasks, beta, slab, ld, gate);
 }
 
-// Wide kernel: 16 elements per thread per row for fp64 (NV = 8), 32 for fp32 (NV = 8) and
-// bf16 (NV = 4); the block size BS (256 / 512) covers ld.  (1024-thread blocks would cap a
+// Wide kernel: 16 elements per thread per row for fp64 accumulators (NV = 8 fp64 rows, NV = 4 fp32 rows: the
+// register tiles are the accumulator's), 32 for fp32 (NV = 8) and bf16 (NV = 4); the block size BS (256 / 512)
+// covers ld.  (1024-thread blocks would cap a
 // wave at 128 VGPRs and spill the two-row register tiles, so wider rows take the two-pass path.)
 template <typename T, typename A, int LOSS>
 static hipError_t launch_wide(int bs, int R, const Segment* segs, const Task* tasks, int ntasks, const A* beta,
                               A* slab, int ld, hipStream_t st, const int* gate) {
-  constexpr int NV = Vec16<T>::N == 8 ? 4 : 8;
+  constexpr int NV = (sizeof(A) == 8 ? 16 : 32) / Vec16<T>::N;
   if (R < 1 || R > 3 || ntasks % R) return hipErrorInvalidValue;
   const dim3 grid(ntasks / R);
   const bool half = static_cast<long long>(bs) * (NV / 2) * Vec16<T>::N >= ld;

@@ -23,8 +23,17 @@ bool strict_release();
 void set_release_form(bool strict);
 
 // ---- worker gradient (grad_dense.hip + slab_reduce.hip, grad_sparse.hip) ---------------
-// dtype: 0 fp64 storage/acc, 1 fp32/fp32, 2 bf16 storage/fp32 acc; loss: 0 logistic, 1 least squares
+// dtype: 0 fp64 storage/acc, 1 fp32/fp32, 2 bf16 storage/fp32 acc, 3 fp32 storage/fp64 acc; loss: 0 logistic,
+// 1 least squares
 // k: the kernel the plan chose (grad_dense.h KernelChoice)
+// The accumulator of a storage code -- its code (0 fp64, 1 fp32: what every launcher below that takes an
+// accumulator / message dtype expects, host_util.h acc_code) and element size -- and the elements of a
+// 16-byte vector of the storage type.  The one place the two codes are related (common.h dispatch_storage
+// instantiates the same pairs); host-includable, so the plan validators use it too.
+constexpr int storage_acc_code(int dtype) { return dtype == 0 || dtype == 3 ? 0 : 1; }
+constexpr int storage_acc_bytes(int dtype) { return storage_acc_code(dtype) == 0 ? 8 : 4; }
+constexpr int storage_vec(int dtype) { return dtype == 0 ? 2 : dtype == 2 ? 8 : 4; }
+constexpr bool storage_code_ok(int dtype) { return dtype >= 0 && dtype <= 3; }
 // Slab-reduction scratch of the dense launchers ("part"): [nslots][kSlabSplits][ld] partial sums in
 // the accumulator type.
 constexpr long long kSlabSplits = 16;  // splits per message of the slab reduction's stage 1 (slab_reduce.hip)

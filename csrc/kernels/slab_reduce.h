@@ -1,4 +1,4 @@
-// Host entry points of the slab reduction (slab_reduce.hip).  dtype: 0 fp64 accumulators, else fp32; slab,
+// Host entry points of the slab reduction (slab_reduce.hip).  dtype: the storage code of launchers.h (fp64 accumulators for 0 and 3, else fp32); slab,
 // part (launchers.h slab_part_bytes) and G [nslots][ld] hold that type; stb [nslots + 1]: each message's slab rows.
 #pragma once
 

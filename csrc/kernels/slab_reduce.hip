@@ -278,9 +278,13 @@ slab_final_update(const A* __restrict__ part, A* __restrict__ G, int ld, int nsl
 void set_slab_reduce_mode(int mode) { g_slab_mode = mode; }
 int slab_reduce_mode() { return g_slab_mode; }
 
-// The accumulator type of a launch's dtype code, chosen here for every entry point: f(A{}).
+// The accumulator type of a launch's storage code (launchers.h storage_acc_code), chosen here for every
+// entry point: f(A{}).
 template <typename F>
-static hipError_t with_acc(int dtype, F&& f) { return dtype == 0 ? f(double{}) : f(float{}); }
+static hipError_t with_acc(int dtype, F&& f) {
+  if (!storage_code_ok(dtype)) return hipErrorInvalidValue;
+  return storage_acc_code(dtype) == 0 ? f(double{}) : f(float{});
+}
 
 hipError_t slab_reduce_launch(int dtype, const void* slab_, const int* stb, void* part_, void* G_, int nslots, int ld,
                               hipStream_t st, const PutDesc* put, const int* gate) {

@@ -19,12 +19,13 @@ std::shared_ptr<GradLauncher> make_dense(int64_t dtype, int64_t loss, int64_t cp
                                          const Tensor& part, int64_t ld, std::optional<Tensor> task_row_off,
                                          std::optional<Tensor> rbuf, const eh::KernelChoice& choice) {
   for (auto* t : {&segs, &tasks, &slab, &stb, &part}) need_gpu(*t, "dense plan operand");
-  need(dtype >= 0 && dtype <= 2, "dtype code must be 0 (fp64), 1 (fp32) or 2 (bf16 storage)");
-  const int ac = dtype == 0 ? 0 : 1;
+  need(eh::storage_code_ok((int)dtype),
+       "dtype code must be 0 (fp64), 1 (fp32), 2 (bf16 storage) or 3 (fp32 storage, fp64 accumulators)");
+  const int ac = eh::storage_acc_code((int)dtype);
   need(tasks.dim() == 2 && tasks.size(1) == 5 && tasks.scalar_type() == at::kInt, "tasks must be int32 [n,5]");
   need(segs.scalar_type() == at::kByte && segs.numel() % 32 == 0, "segs must be packed uint8 [nseg*32]");
   need(stb.scalar_type() == at::kInt && stb.numel() >= 1, "slot_task_begin must be int32 [nslots + 1]");
-  need(ld % (dtype == 0 ? 2 : dtype == 1 ? 4 : 8) == 0, "ld must be a multiple of the 16-byte vector width");
+  need(ld % eh::storage_vec((int)dtype) == 0, "ld must be a multiple of the 16-byte vector width");
   need(slab.dim() == 2 && slab.size(0) >= tasks.size(0) && slab.size(1) == ld && acc_code(slab) == ac,
        "slab must be [>=ntasks, ld] in the accumulator dtype");
   need(acc_code(part) == ac, "part must have the accumulator dtype");
@@ -37,7 +38,7 @@ std::shared_ptr<GradLauncher> make_dense(int64_t dtype, int64_t loss, int64_t cp
   g->ntasks = (int)tasks.size(0);
   g->nslots = (int)stb.numel() - 1;
   g->rows = g->nslots;
-  need(part.numel() * part.element_size() >= eh::slab_part_bytes(g->nslots, ld, dtype == 0 ? 8 : 4),
+  need(part.numel() * part.element_size() >= eh::slab_part_bytes(g->nslots, ld, eh::storage_acc_bytes((int)dtype)),
        "part must hold the slab partial sums (grad.py DenseGradPlan)");
   g->segs = segs.data_ptr();
   g->tasks = tasks.data_ptr();
@@ -59,7 +60,7 @@ std::shared_ptr<GradLauncher> make_dense(int64_t dtype, int64_t loss, int64_t cp
     g->keep.push_back(*rbuf);
   } else {
     need(cpl <= 32 ? cpl * 64 >= ld
-                   : ((cpl == 256 || cpl == 512) && cpl * (dtype == 0 ? 16 : 32) >= ld),
+                   : ((cpl == 256 || cpl == 512) && cpl * (ac == 0 ? 16 : 32) >= ld),  // grad_dense.hip launch_wide
          "cpl (narrow: columns per lane, wide: block size) must cover ld");
     g->kind = 0;
   }

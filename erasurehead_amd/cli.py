@@ -28,7 +28,9 @@ def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="main.py", add_help=True)
     p.add_argument("positional", nargs="*")
     g = p.add_argument_group("extensions (defaults reproduce the reference)")
-    g.add_argument("--precision", default="fp64", choices=["fp64", "fp32", "bf16"])
+    g.add_argument("--precision", default="fp64", choices=["fp64", "fp32", "bf16", "fp32x64"],
+                   help="worker compute: storage / accumulator fp64, fp32, bf16 / fp32, or fp32x64 = fp32 storage "
+                        "with fp64 arithmetic (fp64-grade trajectories at half the HBM bytes)")
     g.add_argument("--loss", default="auto", choices=["auto", *LOSS_CHOICES])
     g.add_argument("--classes", type=int, default=None,
                    help="--loss softmax: number of classes, 2..8 (default 2); labels are class indices 0..C-1")

@@ -43,7 +43,7 @@ class RunConfig:
     lr_decay: float = 0.98  # exponential: eta_i = lr * decay**i, i = 1..R (the regression schedule)
 
     # ---- extensions -----------------------------------------------------------------
-    precision: str = "fp64"  # fp64 | fp32 | bf16 worker compute (master state always fp64)
+    precision: str = "fp64"  # fp64 | fp32 | bf16 | fp32x64 worker compute (master state always fp64)
     loss: str = "auto"  # auto (reference dispatch) | logistic | least_squares | squared_hinge | softmax
     classes: Optional[int] = None  # softmax only: number of classes, 2..8 (default 2)
     seed: Optional[int] = None  # beta_0 / B matrix seed (reference: unseeded)

@@ -23,7 +23,9 @@ from . import io as dio
 from .synthetic import DeviceGMM
 
 
-def _pad_dense(X, prec: Precision, device) -> torch.Tensor:
+def _pad_dense(X, prec: Precision, device, rounding: Optional[List[float]] = None) -> torch.Tensor:
+    """rounding: a one-element list holding the largest |x - fl(x)| / |x| so far of the fp64 originals rounded
+    to the storage precision; updated with this array's (DataSource.storage_max_rel_rounding)."""
     if not isinstance(X, torch.Tensor):  # memory-mapped .npy twins are read-only: copy those
         X = torch.from_numpy(np.require(np.asarray(X, dtype=np.float64), requirements=["W", "C"]))
     if X.dim() == 1:
@@ -31,13 +33,27 @@ def _pad_dense(X, prec: Precision, device) -> torch.Tensor:
     n, d = X.shape
     ld = prec.ld(d)
     out = torch.zeros((n, ld), dtype=prec.storage, device=device)
-    out[:, :d] = X.to(device=device, dtype=torch.float64).to(prec.storage)
+    X64 = X.to(device=device, dtype=torch.float64)
+    out[:, :d] = X64.to(prec.storage)
+    if rounding is not None and prec.storage != torch.float64 and X64.numel():
+        err = (X64 - out[:, :d].double()).abs() / X64.abs()  # 0 / 0 (an exact zero) is no rounding
+        rounding[0] = max(rounding[0], float(torch.nan_to_num(err, nan=0.0, posinf=float("inf")).max()))
     return out
 
 
 class DataSource:
     is_sparse = False
     d: int
+    # largest |x - fl(x)| / |x| over the dense training rows handed out by partition() so far, for sources that
+    # hold fp64 originals (0.0: the storage precision holds them exactly); None: drawn directly in the storage
+    # precision, or sparse (kept in the accumulator precision)
+    storage_max_rel_rounding: Optional[float] = None
+
+    def _padded_partition(self, X, prec: Precision, device) -> torch.Tensor:
+        r = [self.storage_max_rel_rounding or 0.0]
+        out = _pad_dense(X, prec, device, r)
+        self.storage_max_rel_rounding = r[0]
+        return out
 
     def partition(self, p: int, prec: Precision, device):
         raise NotImplementedError
@@ -71,7 +87,7 @@ class FileSource(DataSource):
             raise ValueError(f"partition {p + 1}: {X.shape[0]} rows but {len(y)} labels; check n_rows")
         if self.is_sparse:
             return X, np.asarray(y, dtype=np.float64)
-        return _pad_dense(X, prec, device), torch.tensor(np.asarray(y), dtype=prec.acc, device=device)
+        return self._padded_partition(X, prec, device), torch.tensor(np.asarray(y), dtype=prec.acc, device=device)
 
     def train_eval_chunks(self, parts, prec, device):
         y = self.labels()
@@ -126,7 +142,7 @@ class ArraySource(DataSource):
         X, y = self.parts[p]
         if self.is_sparse:
             return X, np.asarray(y, dtype=np.float64)
-        return _pad_dense(X, prec, device), torch.tensor(np.asarray(y), dtype=prec.acc, device=device)
+        return self._padded_partition(X, prec, device), torch.tensor(np.asarray(y), dtype=prec.acc, device=device)
 
     def train_eval_chunks(self, parts, prec, device):
         ys = np.concatenate([np.asarray(y) for _, y in self.parts])

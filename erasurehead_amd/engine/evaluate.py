@@ -132,9 +132,9 @@ def evaluate(trainer: Trainer, res: TrainResult, log=None, write: bool = True) -
         if trainer.scheme.logs_eval_loading and not trainer.source.is_sparse:
             for p in parts:
                 log(">> Loaded %d" % (p + 1))
-    sums, n_train = loss_sums(_train_chunks(trainer, parts, prec, dev), B, d, kind)
+    sums, n_train = loss_sums(_train_chunks(trainer, parts, prec, dev), B, d, kind, acc=prec)
     Xt, yt = trainer.source.test(prec, dev)
-    P, tsum = predictions_and_loss(Xt, yt, B, d, kind)
+    P, tsum = predictions_and_loss(Xt, yt, B, d, kind, acc=prec)
     n_test = Xt.shape[0]
     training_loss = sums / max(1, n_train)
     testing_loss = tsum / max(1, n_test)

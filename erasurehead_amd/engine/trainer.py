@@ -281,7 +281,7 @@ class Trainer:
             raise MemoryError(
                 f"rank {self.env.rank}: its logical workers need {need_bytes / 2**30:.1f} GiB of resident "
                 f"partitions but only {free / 2**30:.1f} of {total / 2**30:.1f} GiB HBM are free; launch more GPU "
-                f"ranks (torchrun --nproc-per-node) or use --precision fp32/bf16")
+                f"ranks (torchrun --nproc-per-node) or use --precision fp32x64/fp32/bf16")
 
     def _setup_buffers(self):
         cfg, env = self.cfg, self.env
@@ -765,6 +765,8 @@ class Trainer:
         kern = self._kernel_label()
         if kern:
             rep["grad_kernel"] = kern
+        # what storing the rows in the precision's storage type cost (data/source.py): 0.0 = nothing
+        rep["storage_max_rel_rounding"] = getattr(self.source, "storage_max_rel_rounding", None)
         if self.tx is not None and self.tx.name in P2P_TRANSPORTS:
             from .. import HW_QUEUES
 

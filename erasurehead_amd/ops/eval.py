@@ -103,17 +103,25 @@ def sparse_eval_device(X, y: torch.Tensor, Bt: torch.Tensor, kind: int, want_P: 
     return P, s
 
 
+def _dense_acc(X: torch.Tensor, acc=None):
+    """Accumulator dtype of a dense evaluation: ``acc`` (a Precision, or a torch dtype) when given -- fp32 rows
+    under ``fp32x64`` multiply in fp64 -- else the default rule, fp64 for fp64 rows and fp32 otherwise."""
+    if acc is not None:
+        return getattr(acc, "acc", acc)
+    return torch.float64 if X.dtype == torch.float64 else torch.float32
+
+
 def _transposed(B: torch.Tensor, acc) -> torch.Tensor:
     return B.to(acc).t().contiguous()
 
 
-def predictions(X, B: torch.Tensor, d: int) -> torch.Tensor:
-    """P = X[:, :d] @ B[:, :d]^T  ([n, R], accumulator dtype of X)."""
+def predictions(X, B: torch.Tensor, d: int, acc=None) -> torch.Tensor:
+    """P = X[:, :d] @ B[:, :d]^T  ([n, R], accumulator dtype: :func:`_dense_acc`)."""
     if _is_sparse(X):
         Xt = _to_torch_sparse(X, B.device, torch.float64)
         return (Xt @ B[:, :d].double().t().contiguous())
     n = X.shape[0]
-    acc = torch.float64 if X.dtype == torch.float64 else torch.float32
+    acc = _dense_acc(X, acc)
     Bc = B.to(acc).contiguous()
     if X.is_cuda:
         P = torch.empty((n, B.shape[0]), dtype=acc, device=X.device)
@@ -124,23 +132,25 @@ def predictions(X, B: torch.Tensor, d: int) -> torch.Tensor:
     return X[:, :d].to(acc) @ Bc[:, :d].t()
 
 
-def predictions_and_loss(X, y: torch.Tensor, B: torch.Tensor, d: int, kind: int) -> Tuple[torch.Tensor, np.ndarray]:
+def predictions_and_loss(X, y: torch.Tensor, B: torch.Tensor, d: int, kind: int,
+                         acc=None) -> Tuple[torch.Tensor, np.ndarray]:
     """(P = X B^T, per-beta loss sums) — on the GPU one MFMA GEMM with the loss fused in its epilogue."""
     if _is_sparse(X) and B.is_cuda:
         P, s = sparse_eval_device(X, y, _transposed(B, torch.float64), kind, True)
         return P, s.cpu().numpy()
     if not _is_sparse(X) and X.is_cuda:
         n = X.shape[0]
-        acc = torch.float64 if X.dtype == torch.float64 else torch.float32
+        acc = _dense_acc(X, acc)
         P = torch.empty((n, B.shape[0]), dtype=acc, device=X.device)
         s = torch.zeros(B.shape[0], dtype=torch.float64, device=X.device)
         native().eval_gemm_loss(kind, X, n, d, y.to(acc).contiguous(), B.to(acc).contiguous(), s, P)
         return P, s.cpu().numpy()
-    P = predictions(X, B, d)
+    P = predictions(X, B, d, acc)
     return P, _loss_torch(kind, y.to(P.device), P).double().cpu().numpy()
 
 
-def loss_sums(chunks: Iterable[Tuple[object, torch.Tensor]], B: torch.Tensor, d: int, kind: int) -> Tuple[np.ndarray, int]:
+def loss_sums(chunks: Iterable[Tuple[object, torch.Tensor]], B: torch.Tensor, d: int, kind: int,
+              acc=None) -> Tuple[np.ndarray, int]:
     """Sum over all chunk rows of the per-row loss for every beta row of B -> ([R], n)."""
     R = B.shape[0]
     total = None
@@ -155,11 +165,11 @@ def loss_sums(chunks: Iterable[Tuple[object, torch.Tensor]], B: torch.Tensor, d:
             P = predictions(X, B, d)
             s = _loss_torch(kind, y.to(P.device), P)
         elif X.is_cuda:
-            acc = torch.float64 if X.dtype == torch.float64 else torch.float32
+            a = _dense_acc(X, acc)
             s = torch.zeros(R, dtype=torch.float64, device=X.device)
-            native().eval_gemm_loss(kind, X, X.shape[0], d, y.to(acc).contiguous(), B.to(acc).contiguous(), s, None)
+            native().eval_gemm_loss(kind, X, X.shape[0], d, y.to(a).contiguous(), B.to(a).contiguous(), s, None)
         else:
-            P = predictions(X, B, d)
+            P = predictions(X, B, d, acc)
             s = _loss_torch(kind, y, P)
         total = s if total is None else total + s.to(total.device)
         n += X.shape[0]

@@ -104,12 +104,18 @@ class KernelChoice:
         return out
 
 
-def multi_slots(distinct_rows: int, fp32: bool = False, n_cus: int = N_CUS, cpl: int = 16) -> int:
+def multi_slots(distinct_rows: int, fp32: bool = False, n_cus: int = N_CUS, cpl: int = 16, x64: bool = False) -> int:
     """Resident one-wave bundles of grad_dense_multi on the chip (4 per folded workgroup).  ``fp32``
     selects the 12 / 8-per-CU rule measured for fp32 in round 3; since round 5 it sizes bf16 distinct
     rows and fp32 rows narrower than 16 columns per lane only, while fp32 rows of 16 columns per lane
-    take the fp64 rule (choose_kernel; profiles/round5/shapes/fp32_*)."""
+    take the fp64 rule (choose_kernel; profiles/round5/shapes/fp32_*).  ``x64``: replica bundles of fp32
+    rows with fp64 accumulators -- the fp64 rule, but two workgroups per CU on long streams (4 KB rows: 4 waves
+    with one row ahead keep half of fp64's bytes in flight; AGC R = 3 at 1e6 x 1000 rows 512-row bundles 0.627 ms
+    vs 1024-row 0.673, FRC R = 2 0.596 vs 0.606, while at 125k rows one per CU stays ahead, 0.093 vs 0.095;
+    docs/PERF_NOTES.md, fp32x64)."""
     long_stream = distinct_rows >= LONG_STREAM_ROWS_PER_CU * n_cus
+    if x64 and long_stream and not fp32:
+        return 8 * max(1, 16 // cpl) * n_cus
     # fp64: one workgroup (4 bundles) per CU.  Since a step waits for its own row only (the label
     # load behind the row), 4 waves with the next row in flight keep a CU's share of HBM busy, and
     # half as many slab rows, betas and folds are paid (profiles/round3/rows_prefetch: 1024 / 512 /
@@ -121,7 +127,7 @@ def multi_slots(distinct_rows: int, fp32: bool = False, n_cus: int = N_CUS, cpl:
 
 
 def multi_bundle_rows(distinct_rows: int, fp32: bool = False, n_cus: int = N_CUS, cpl: int = 16,
-                      part_rows: Optional[Sequence[int]] = None) -> int:
+                      part_rows: Optional[Sequence[int]] = None, x64: bool = False) -> int:
     """Rows per one-wave bundle of grad_dense_multi: the shortest multiple of 32 rows whose folded
     workgroups (4 bundles of one partition each, the last one per partition padded) all fit the
     chip's resident slots at once, so every bundle starts in the first dispatch round and no CU is
@@ -137,7 +143,7 @@ def multi_bundle_rows(distinct_rows: int, fp32: bool = False, n_cus: int = N_CUS
     distinct rows -> 512 / 256 / 128 / 64-row bundles, 1.195 / 0.600 / 0.312 / 0.169 ms (768 rows,
     the default before nt: 1.26 ms; 384: 1.42 = a second partial round); fp32 -> 352 / 192 / 96 /
     64 rows (192: 0.333 vs 256: 0.341-0.350 ms at 500k; 96: 0.177 vs 128: 0.186 at 250k)."""
-    slots = multi_slots(distinct_rows, fp32, n_cus, cpl)
+    slots = multi_slots(distinct_rows, fp32, n_cus, cpl, x64)
     parts = [int(r) for r in part_rows if r > 0] if part_rows else [distinct_rows / 8.0] * 8
     per = distinct_rows / slots
     # small problems: bundles down to 8 rows (a wave with one row ahead streams ~1.4 us per row, so a
@@ -231,7 +237,9 @@ def choose_kernel(prec_code: int, ld: int, cpl: Optional[int], max_rep: int, dis
                   n_cus: int = N_CUS, part_rows: Optional[Sequence[int]] = None) -> KernelChoice:
     """The measured default kernel of a plan (a pure function; tests/test_plan_tables.py pins the table).
 
-    prec_code: 0 fp64, 1 fp32, 2 bf16 storage.  max_rep: most co-located messages reading one
+    prec_code: 0 fp64, 1 fp32, 2 bf16 storage, 3 fp32 storage with fp64 accumulators (``fp32x64``: the row
+    geometry ``cpl`` is the storage's, every residency rule below is the fp64 one -- the register tiles
+    and slab rows are the accumulator's -- and the wide tile is 16 elements per thread).  max_rep: most co-located messages reading one
     partition (1 = distinct rows only).  distinct_rows: rows of the distinct partitions per round.
     Measured choices (docs/PERF_NOTES.md):
       * distinct rows (naive, message-placed ranks): one-wave bundles of one replica at 16 columns per
@@ -257,12 +265,13 @@ def choose_kernel(prec_code: int, ld: int, cpl: Optional[int], max_rep: int, dis
     """
     if cpl is None:
         return KernelChoice("twopass")
+    storage_code, prec_code = prec_code, ACC_RULES.get(prec_code, prec_code)  # rules by accumulator
     shared = max_rep > 1
     if cpl >= 256:
         if shared and cpl == 256 and max_rep <= 3:
             return KernelChoice("wide", replicas=max_rep,
                                 bundle_rows=wide_bundle_rows(distinct_rows, n_cus, part_rows,
-                                                             wide_slots_per_cu(prec_code, ld, max_rep)))
+                                                             wide_slots_per_cu(storage_code, ld, max_rep)))
         return KernelChoice("wide", interleave=shared)
     if not shared:
         if 8 < cpl <= 16:  # distinct rows of 16 columns per lane: bundles of one
@@ -273,6 +282,16 @@ def choose_kernel(prec_code: int, ld: int, cpl: Optional[int], max_rep: int, dis
             return KernelChoice("multi", replicas=1,
                                 bundle_rows=multi_bundle_rows(distinct_rows, prec_code == 2, n_cus, cpl, part_rows),
                                 fold=True)
+        if storage_code == 3 and cpl == 32:
+            # fp32 rows, fp64 accumulators, 32 columns per lane: one row in flight.  The pair kernel holds 323-360
+            # VGPRs there (one wave per SIMD, and an fp32 row is half of fp64's bytes in flight): d = 2048, 1e6 rows
+            # 1.279 ms vs 3.595 (1e5: 0.161 vs 0.431; LDS-staged 1.416, wide rows 1.771; docs/PERF_NOTES.md, fp32x64)
+            return KernelChoice("fused", rows=1)
+        if storage_code == 3 and cpl <= 4:
+            # ... of at most 4 columns per lane (d <= 256): pair-row one-wave bundles of one replica, d = 256 1e6
+            # rows 0.179 ms vs 0.266 fused (8 columns per lane, d = 512, was not measured and keeps the fp64 rule)
+            return KernelChoice("multi", replicas=1, bundle_rows=pair_bundle_rows(distinct_rows, n_cus, False, cpl),
+                                fold=True, pair=True)
         return KernelChoice("fused", rows={0: 2, 1: 4, 2: 1}[prec_code])
     long_stream = distinct_rows >= LONG_STREAM_ROWS_PER_CU * n_cus
     if prec_code == 2:
@@ -290,16 +309,20 @@ def choose_kernel(prec_code: int, ld: int, cpl: Optional[int], max_rep: int, dis
         # fp64 rows of 32 columns per lane (1024 < d <= 2048): 256-thread wide-row bundles (the
         # half-width instance) over the LDS-staged pair form: d = 2048 1e6 rows 2.466 vs 2.719 ms, 1e5
         # rows 0.268 vs 0.335 (profiles/round4/r4i/choices.jsonl)
-        return KernelChoice("wide", replicas=max_rep,
-                            bundle_rows=wide_bundle_rows(distinct_rows, n_cus, part_rows,
-                                                         wide_slots_per_cu(prec_code, ld, max_rep)))
+        rows = wide_bundle_rows(distinct_rows, n_cus, part_rows, wide_slots_per_cu(storage_code, ld, max_rep))
+        if storage_code == 3:
+            # fp32 rows, fp64 accumulators: at most 208 rows per bundle (the half-width instance holds 116-146 VGPRs,
+            # so more than two workgroups fit a CU and short bundles measured faster): d = 2048 R = 3 1e6 rows 2.028 ms
+            # vs 2.423 with 1968-row bundles (128 / 256 / 512 rows: 2.060 / 2.081 / 2.153; 1e5 rows: 208 either way)
+            rows = min(rows, 208)
+        return KernelChoice("wide", replicas=max_rep, bundle_rows=rows)
     if cpl <= 16 and max_rep in (2, 3):
         # fp32 rows of 16 columns per lane size their replica bundles like fp64 (one folded workgroup per
         # CU): AGC R = 3 at the 1 / 2 / 4 / 8-GPU rank shapes 586.7 / 299.0 / 155.5 / 86.3 us vs 587.6 /
         # 303.4 / 170.6 / 87.4 with the 12-per-CU fp32 sizing (profiles/round5/shapes/fp32_rows_*.jsonl)
         return KernelChoice("multi", replicas=max_rep,
                             bundle_rows=multi_bundle_rows(distinct_rows, prec_code == 1 and cpl < 16, n_cus, cpl,
-                                                          part_rows),
+                                                          part_rows, x64=storage_code == 3),
                             fold=True, lane_epi=True)
     # more replicas than a workgroup's task slots: bundles of MAX_BUNDLE (and the remainder, padded)
     return KernelChoice("staged", replicas=min(max_rep, MAX_BUNDLE),
@@ -312,9 +335,9 @@ def wide_slots_per_cu(prec_code: int, ld: int, replicas: int) -> int:
     kernel's vectors at 256 threads (fp32 d <= 4096, bf16 <= 4096) take the NV / 2 instance, two or
     more per CU (fp32 d <= 2048: the NV / 4 instance, counted as four); full-width replica rows (fp64
     d > 2048, fp32 > 4096) run 512-thread workgroups of about 150 VGPRs, one per CU."""
-    vec = {0: 2, 1: 4, 2: 8}[prec_code]
-    half = 256 * (WIDE_EPT[vec] // 2) >= ld
-    quarter = prec_code == 1 and 256 * (WIDE_EPT[vec] // 4) >= ld  # fp32 d <= 2048: the quarter instance
+    ept = 16 if prec_code == 3 else WIDE_EPT[{0: 2, 1: 4, 2: 8}[prec_code]]  # (fp32x64: wide_ept, fp64's tile)
+    half = 256 * (ept // 2) >= ld
+    quarter = prec_code == 1 and 256 * (ept // 4) >= ld  # fp32 d <= 2048: the quarter instance
     return 4 if quarter else 2 if replicas <= 1 or half else 1
 
 
@@ -338,10 +361,21 @@ def wide_bundle_rows(distinct_rows: int, n_cus: int = N_CUS, part_rows: Optional
 
 
 WIDE_EPT = {2: 16, 4: 32, 8: 32}  # elements per thread per row of grad_dense_wide (by vector width)
+# Storage codes whose residency rules are another code's (choose_kernel): fp32 rows with fp64 accumulators hold
+# fp64's register tiles, slab rows and folds.
+ACC_RULES = {3: 0}
 
 
-def choose_cpl(ld: int, vec: int) -> Optional[int]:
-    """Kernel selector of the single-pass dense gradient.
+def wide_ept(prec: Precision) -> int:
+    """Elements per thread per row of grad_dense_wide for a precision: the tile is sized by the accumulator's
+    registers (grad_dense.hip launch_wide), so fp32 rows with fp64 accumulators take fp64's 16, not
+    ``WIDE_EPT[prec.vec]``."""
+    return 16 if prec.acc == torch.float64 else WIDE_EPT[prec.vec]
+
+
+def choose_cpl(ld: int, vec: int, ept: Optional[int] = None) -> Optional[int]:
+    """Kernel selector of the single-pass dense gradient.  ept: elements per thread of the wide kernel
+    (:func:`wide_ept`; default ``WIDE_EPT[vec]``).
 
     2..32       grad_dense_fused: a wave owns a row, ``cpl`` columns per lane (64 * cpl >= ld)
     256, 512    grad_dense_wide: a workgroup of that many threads owns a row (wide d)
@@ -351,7 +385,7 @@ def choose_cpl(ld: int, vec: int) -> Optional[int]:
         if c % vec == 0 and 64 * c >= ld:
             return c
     for bs in (256, 512):
-        if bs * WIDE_EPT[vec] >= ld:
+        if bs * (ept or WIDE_EPT[vec]) >= ld:
             return bs
     return None
 
@@ -434,7 +468,7 @@ class DenseGradPlan:
             if y.shape[0] != X.shape[0] or y.dtype != prec.acc:
                 raise ValueError(f"partition {p}: y must be [{X.shape[0]}] {prec.acc}")
         self.total_rows = sum(partitions[p][0].shape[0] for m in self.messages for p, _ in m)
-        self.cpl = choose_cpl(self.ld, prec.vec)
+        self.cpl = choose_cpl(self.ld, prec.vec, wide_ept(prec))
         # co-located replicas: a partition read by several local messages (an empty partition has no rows
         # to share: counting it would pick a replica kernel for bundles that hold fewer replicas)
         self.max_rep = max(collections.Counter(p for m in self.messages for p, _ in m

@@ -3,6 +3,10 @@
   fp64  X fp64, accumulate fp64 — bit-compatible math with the reference's NumPy float64
   fp32  X fp32, accumulate fp32
   bf16  X stored bf16 (half the HBM bytes of fp32), accumulate fp32
+  fp32x64  X stored fp32 (half the HBM bytes of fp64), everything computed from it in fp64: the dot
+           product, residual, gradient accumulators, slab, messages, decode and update are the fp64
+           run's.  The one deviation from fp64 is a single rounding of X at load (2^-24 relative; none
+           for data that is exact in fp32: one-hot, integer features, files written with few digits)
 
 beta, u and the betaset history are always fp64 on the master (update kernel), the
 per-round worker copy of beta and the gradient messages use the accumulator type.
@@ -17,7 +21,7 @@ import torch
 @dataclass(frozen=True)
 class Precision:
     name: str
-    code: int  # kernel dtype code
+    code: int  # kernel storage code (csrc/kernels/launchers.h): selects (storage, accumulator) together
     storage: torch.dtype
     acc: torch.dtype
     vec: int  # elements per 16-byte vector load
@@ -35,6 +39,7 @@ PRECISIONS = {
     "fp64": Precision("fp64", 0, torch.float64, torch.float64, 2),
     "fp32": Precision("fp32", 1, torch.float32, torch.float32, 4),
     "bf16": Precision("bf16", 2, torch.bfloat16, torch.float32, 8),
+    "fp32x64": Precision("fp32x64", 3, torch.float32, torch.float64, 4),
 }
 
 

@@ -53,6 +53,8 @@ class SoftmaxGradPlan:
             raise ValueError(f"softmax: classes must be in {MIN_CLASSES}..{MAX_CLASSES}, got {classes}")
         if prec.name == "bf16":
             raise ValueError("softmax: bf16 storage is not supported (fp64 or fp32)")
+        if prec.name == "fp32x64":  # the multi-class kernel has no fp32-storage, fp64-accumulator instance yet
+            raise ValueError("softmax: fp32x64 (fp32 storage, fp64 arithmetic) is not supported (fp64 or fp32)")
         if sparse:
             raise ValueError("softmax: sparse data sources are not supported (dense partitions only)")
 

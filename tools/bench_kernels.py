@@ -335,7 +335,7 @@ def main():
     ap.add_argument("--only", choices=["dense", "sparse", "scale", "eval", "sweep", "choices"], default=None)
     ap.add_argument("--ds", default="256,1000,2048,4096", help="--only sweep: row widths")
     ap.add_argument("--ns", default="1e5,1e6,4e6", help="--only sweep: row counts")
-    ap.add_argument("--precs", default="fp64,fp32", help="--only sweep: precisions")
+    ap.add_argument("--precs", default="fp64,fp32", help="--only sweep: precisions (fp64, fp32, bf16, fp32x64)")
     ap.add_argument("--loss", default="logistic",
                     help="--only sweep: losses timed on the same data, in order (logistic, least_squares, squared_hinge, "
                          "softmax)")

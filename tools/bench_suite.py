@@ -129,7 +129,7 @@ def run_child(name, a) -> dict:
 
     with tempfile.TemporaryDirectory() as tmp:
         cmd = [sys.executable, os.path.abspath(__file__), "--only", name, "--in-process", "--out", tmp,
-               "--device-loop", a.device_loop] + (["--quick"] if a.quick else [])
+               "--device-loop", a.device_loop, "--precision", a.precision] + (["--quick"] if a.quick else [])
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         if out.returncode != 0:
             raise RuntimeError(f"{name}: child exited {out.returncode}: {out.stderr[-2000:]}")
@@ -143,6 +143,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out"))
     ap.add_argument("--only", default=None, help="comma-separated config names")
     ap.add_argument("--device-loop", default="auto", choices=["auto", "graph", "stream", "off"])
+    ap.add_argument("--precision", default="fp64", choices=["fp64", "fp32", "bf16", "fp32x64"],
+                    help="worker precision of the dense configs (the one-hot configs keep fp64)")
     ap.add_argument("--in-process", action="store_true",
                     help="run the dense configs in this process too (default: one fresh process each, like bench.py: "
                          "8 GB of X allocated after another config's freed 8 GB streamed up to 9 %% slower)")
@@ -153,7 +155,7 @@ def main():
     scale = 10 if a.quick else 1
     n_dense = 1_000_000 // scale
     dense = dict(n_procs=9, n_rows=n_dense, n_cols=1000, input_dir="/tmp/eh_suite/", is_real=0, dataset="synthetic",
-                 data="synthetic", data_seed=1234, update_rule="AGD")
+                 data="synthetic", data_seed=1234, update_rule="AGD", precision=a.precision)
     configs = []
     # (name, RunConfig kwargs, data source, delay-floor kwargs, instrumented, data family)
     configs.append(("naive_dense", dict(dense, is_coded=0), None, None, False, "dense"))
