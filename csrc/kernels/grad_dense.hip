@@ -28,6 +28,7 @@
 #include "grad_dense.h"
 #include "launchers.h"
 #include "lds_dma.h"
+#include "pack58.h"
 #include "slab_reduce.h"
 
 namespace eh {
@@ -1264,7 +1265,11 @@ static hipError_t launch_fused_cpl(int cpl, const Segment* segs, const Task* tas
 // The gradient kernel the plan chose, for the launch's loss and storage codes: one slab row per task.
 static hipError_t launch_gradient(int dtype, int loss, int cpl, const void* segs, const void* tasks, int ntasks,
                                   const void* beta, void* slab, int ld, hipStream_t st, const KernelChoice& k,
-                                  const int* gate) {
+                                  const int* gate, const PackedRows* packed) {
+  if (packed) {  // a packed plan (grad_dense_packed.hip): fp64 one-wave folded bundles of 16 columns per lane
+    if (dtype != 0 || cpl != 16) return hipErrorInvalidValue;
+    return grad_dense_packed_launch(loss, segs, tasks, ntasks, beta, slab, ld, st, k, *packed, gate, g_stamps);
+  }
   const Segment* S = static_cast<const Segment*>(segs);
   const Task* Tk = static_cast<const Task*>(tasks);
   return dispatch_loss(loss, [&](auto L) {
@@ -1279,19 +1284,20 @@ static hipError_t launch_gradient(int dtype, int loss, int cpl, const void* segs
 hipError_t grad_dense_launch(int dtype, int loss, int cpl, const void* segs, const void* tasks,
                              int ntasks, const void* beta, void* slab, const int* slot_task_begin,
                              int nslots, void* part, void* G, int ld, hipStream_t st, const KernelChoice& k,
-                             const PutDesc* put, const int* gate) {
-  const hipError_t e = launch_gradient(dtype, loss, cpl, segs, tasks, ntasks, beta, slab, ld, st, k, gate);
+                             const PutDesc* put, const int* gate, const PackedRows* packed) {
+  const hipError_t e = launch_gradient(dtype, loss, cpl, segs, tasks, ntasks, beta, slab, ld, st, k, gate, packed);
   if (e != hipSuccess) return e;
   return slab_reduce_launch(dtype, slab, slot_task_begin, part, G, nslots, ld, st, put, gate);
 }
 
 hipError_t grad_dense_update_launch(int dtype, int loss, int cpl, const void* segs, const void* tasks, int ntasks,
                                     const void* beta, void* slab, const int* stb, int nslots, void* part, void* G,
-                                    int ld, hipStream_t st, const KernelChoice& k, const LocalUpdate& up) {
+                                    int ld, hipStream_t st, const KernelChoice& k, const LocalUpdate& up,
+                                    const PackedRows* packed) {
   if (nslots < 1 || nslots > kMaxMsgs || up.nmsg < 0 || up.nmsg > kMaxMsgs || !up.beta) return hipErrorInvalidValue;
   for (int m = 0; m < up.nmsg; ++m)
     if (up.slot[m] < 0 || up.slot[m] >= nslots) return hipErrorInvalidValue;
-  const hipError_t e = launch_gradient(dtype, loss, cpl, segs, tasks, ntasks, beta, slab, ld, st, k, nullptr);
+  const hipError_t e = launch_gradient(dtype, loss, cpl, segs, tasks, ntasks, beta, slab, ld, st, k, nullptr, packed);
   if (e != hipSuccess) return e;
   return slab_reduce_update_launch(dtype, slab, stb, part, G, nslots, ld, st, up);
 }

@@ -56,12 +56,24 @@ void set_mfma_stream(int mode);  // packed bf16 bundles: 0 LDS-DMA ring (default
 // into `stamps` (int64 [4 * bundles]); nullptr turns it off (tools/probes/bundle_stamps.py).
 void set_grad_stamps(void* stamps);
 int slab_reduce_mode();
+// 58-bit packed copy of fp64 rows (pack58.h): packed dense plans stream it instead of the fp64 rows.
+struct PackedRows;
+// Plan time (pack58.hip): pack the rows of every bundle of the bundle table (R task slots per bundle) into
+// rows[seg] with window e0[seg], compare every decoded value with its source, flags[bundle] = 1 iff all equal.
+hipError_t pack58_launch(const void* segs, const void* tasks, int ntasks, int R, void* const* rows, const int* e0,
+                         int* flags, int ld, hipStream_t st);
+// grad_dense_multi over the packed copy (grad_dense_packed.hip): fp64, 16 columns per lane, folded; bit-identical
+// slab rows.  grad_dense_launch / grad_dense_update_launch call it when given a PackedRows.
+hipError_t grad_dense_packed_launch(int loss, const void* segs, const void* tasks, int ntasks, const void* beta,
+                                    void* slab, int ld, hipStream_t st, const KernelChoice& k, const PackedRows& pk,
+                                    const int* gate, long long* stamps);
 // put (optional): fuse the message put + signal into the final slab reduction; put->dst
 // receives the nslots x ld result rows, put->bytes is ignored.
 hipError_t grad_dense_launch(int dtype, int loss, int cpl, const void* segs, const void* tasks,
                              int ntasks, const void* beta, void* slab, const int* slot_task_begin,
                              int nslots, void* part, void* G, int ld, hipStream_t st, const KernelChoice& k,
-                             const PutDesc* put = nullptr, const int* gate = nullptr);
+                             const PutDesc* put = nullptr, const int* gate = nullptr,
+                             const PackedRows* packed = nullptr);
 hipError_t grad_dense_twopass_launch(int dtype, int loss, const void* segs, const void* tasks,
                                      int ntasks, const void* beta, const int* task_row_off,
                                      void* rbuf, void* slab, const int* slot_task_begin,
@@ -192,7 +204,8 @@ struct LocalUpdate {
 // slab_final_update); bitwise equal to grad_dense_launch followed by combine_update_launch.
 hipError_t grad_dense_update_launch(int dtype, int loss, int cpl, const void* segs, const void* tasks, int ntasks,
                                     const void* beta, void* slab, const int* slot_task_begin, int nslots, void* part,
-                                    void* G, int ld, hipStream_t st, const KernelChoice& k, const LocalUpdate& up);
+                                    void* G, int ld, hipStream_t st, const KernelChoice& k, const LocalUpdate& up,
+                                    const PackedRows* packed = nullptr);
 
 // msg dtype / worker-beta dtype: 0 fp64, 1 fp32; rule 0 GD, 1 AGD
 hipError_t combine_update_launch(const CombineArgs& args, int msg_dtype, int w_dtype,

@@ -318,6 +318,55 @@ void bind_grad_launcher(py::module& m) {
              g.enc_coef = coef.data_ptr<double>();
              for (auto* t : {&ptr, &idx, &coef, &Gb}) g.keep.push_back(*t);
            })
+      // Packed dense plan (ops/grad.py DenseGradPlan, kernels/pack58.h): rows[s] is the 7424-byte-per-row copy of
+      // segment s's partition (replica segments share one tensor), seg_rows[s] its row count, e0 [nseg] the exponent
+      // windows.  Packs every bundle's rows on the current stream, compares them with the source and fills
+      // flags [bundles]; every launch from then on streams the packed rows of the bundles flagged 1.
+      .def(
+          "set_packed",
+          [](GradLauncher& g, const std::vector<Tensor>& rows, const std::vector<int64_t>& seg_rows, const Tensor& e0,
+             const Tensor& flags, bool pack) {
+            const int R = g.choice.replicas;
+            need(g.kind == 0 && g.dtype == 0 && g.cpl == 16 && g.choice.kind == eh::kGradMulti && g.choice.fold &&
+                     !g.choice.pair && g.ld > 512 && g.ld <= eh::p58::kCols && R >= 1 && R <= 3 && g.ntasks > 0 &&
+                     g.ntasks % (4 * R) == 0 && !g.packed,
+                 "set_packed: fp64 folded one-wave bundles of 16 columns per lane only, once per launcher");
+            const int64_t nseg = g.keep[0].numel() / 32;
+            need((int64_t)rows.size() == nseg && (int64_t)seg_rows.size() == nseg, "set_packed: one packed copy per segment");
+            need_gpu(e0, "e0");
+            need_gpu(flags, "flags");
+            need(e0.scalar_type() == at::kInt && e0.numel() == nseg && e0.is_contiguous(), "e0: int32 [segments]");
+            need(flags.scalar_type() == at::kInt && flags.numel() == g.ntasks / R && flags.is_contiguous(),
+                 "flags: int32 [bundles]");
+            const Tensor eh0 = e0.cpu();
+            std::vector<int64_t> ptrs;
+            for (int64_t s = 0; s < nseg; ++s) {
+              need_gpu(rows[s], "packed rows");
+              need(rows[s].scalar_type() == at::kByte && rows[s].is_contiguous() && seg_rows[s] >= 0 &&
+                       rows[s].numel() >= seg_rows[s] * eh::p58::kRowBytes &&
+                       reinterpret_cast<uintptr_t>(rows[s].data_ptr()) % 128 == 0,
+                   "packed rows: uint8 [rows * 7424], 128-byte aligned");
+              const int e = eh0.data_ptr<int>()[s];
+              need(e >= eh::p58::kE0Min && e <= eh::p58::kE0Max, "e0: a window of 31 normal binades");
+              ptrs.push_back(static_cast<int64_t>(reinterpret_cast<uintptr_t>(rows[s].data_ptr())));
+            }
+            const Tensor ptr = torch::tensor(ptrs, torch::dtype(torch::kLong)).to(flags.device());
+            void* const* P = reinterpret_cast<void* const*>(ptr.data_ptr<int64_t>());
+            if (pack)  // (false: a further launcher of a plan whose first launcher packed these tensors)
+              hcheck(eh::pack58_launch(g.segs, g.tasks, g.ntasks, R, P, e0.data_ptr<int>(), flags.data_ptr<int>(),
+                                       g.ld, eh::stream_of(flags)),
+                     "GradLauncher.set_packed");
+            g.pk.rows = reinterpret_cast<const void* const*>(P);
+            g.pk.e0 = e0.data_ptr<int>();
+            g.pk.flags = flags.data_ptr<int>();
+            g.packed = true;
+            g.keep.push_back(ptr);
+            g.keep.push_back(e0);
+            g.keep.push_back(flags);
+            for (const Tensor& t : rows) g.keep.push_back(t);
+          },
+          py::arg("rows"), py::arg("seg_rows"), py::arg("e0"), py::arg("flags"), py::arg("pack") = true)
+      .def_property_readonly("packed", [](const GradLauncher& g) { return g.packed; })
       .def(
           "launch",
           [](const GradLauncher& g, const Tensor& beta, const Tensor& G, std::optional<Tensor> gate) {

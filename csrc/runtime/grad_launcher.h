@@ -9,6 +9,7 @@
 
 #include "kernels/grad_dense.h"
 #include "kernels/launchers.h"
+#include "kernels/pack58.h"
 #include "runtime/host_util.h"
 
 namespace eh {
@@ -37,6 +38,10 @@ struct GradLauncher {
   const int* enc_idx = nullptr;
   const double* enc_coef = nullptr;
   int enc_slots = 0;
+  // packed dense plans (set_packed): the 58-bit copy of every segment's rows and the bundle flags
+  PackedRows pk{};
+  bool packed = false;
+  const PackedRows* packed_rows() const { return packed ? &pk : nullptr; }
   std::vector<at::Tensor> keep;
 
   // The operand checks of a launch from Python (the pumps pass pointers they validated themselves).
@@ -71,18 +76,18 @@ struct GradLauncher {
   bool can_fuse_update() const { return kind == 0 && !Gb && ntasks > 0; }
   hipError_t launch_update(const void* beta, void* G, const LocalUpdate& up, hipStream_t st) const {
     return grad_dense_update_launch(dtype, loss, cpl, segs, tasks, ntasks, beta, slab, stb, nslots, part, G, ld, st,
-                                    choice, up);
+                                    choice, up, packed_rows());
   }
   hipError_t launch_put(const void* beta, void* G, const PutDesc& put, hipStream_t st) const {
     return grad_dense_launch(dtype, loss, cpl, segs, tasks, ntasks, beta, slab, stb, nslots, part, G, ld, st, choice,
-                             &put, put.gate);
+                             &put, put.gate, packed_rows());
   }
 
   hipError_t launch_raw(const void* beta, void* G, hipStream_t st, const int* gate = nullptr) const {
     switch (kind) {
       case 0:
         return ntasks ? grad_dense_launch(dtype, loss, cpl, segs, tasks, ntasks, beta, slab, stb, nslots, part, G, ld,
-                                          st, choice, nullptr, gate)
+                                          st, choice, nullptr, gate, packed_rows())
                       : hipSuccess;
       case 1:
         return ntasks ? grad_dense_twopass_launch(dtype, loss, segs, tasks, ntasks, beta, task_row_off, rbuf, slab, stb,

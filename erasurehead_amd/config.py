@@ -83,6 +83,7 @@ class RunConfig:
     transport: str = "auto"  # auto | ipc | rccl | gloo (parallel/transport.py)
     device_loop: str = "auto"  # auto|graph|stream|off: device-driven rounds when eligible (trainer._device_loop_mode)
     share_partitions: bool = False  # co-located workers: distinct partitions once + device encode (ops/grad.py)
+    pack: str = "auto"  # auto|off: long fp64 streams read the lossless 58-bit copy of X (ops/grad.py pack_auto)
     # simultaneous arrivals (add_delay = 0, or one kernel finishing several local workers): "permute"
     # orders them by a per-round permutation seeded by (tie_seed, round) (csrc/runtime/collector.h,
     # tie model); "worker" keeps worker-id order (AGC then stops on the same k workers every round)

@@ -265,6 +265,8 @@ class Trainer:
             if source.is_sparse:
                 return SparseGradPlan(messages, parts, self.prec, self.loss, self.d, device=dev)
             kw = {"target_tasks": cfg.tasks} if cfg.tasks else {}
+            if cfg.pack == "off":
+                kw["pack"] = False
             return DenseGradPlan(messages, parts, self.prec, self.loss, self.d, **kw)
 
         share = cfg.share_partitions and self.loss != SOFTMAX
@@ -765,6 +767,11 @@ class Trainer:
         kern = self._kernel_label()
         if kern:
             rep["grad_kernel"] = kern
+        inner = getattr(getattr(self, "plan", None), "inner", getattr(self, "plan", None))
+        if hasattr(inner, "packed_bundles"):  # dense plans: bundles streaming the 58-bit copy / the fp64 rows
+            rep["packed_bundles"] = inner.packed_bundles
+            rep["plain_bundles"] = inner.plain_bundles
+            rep["x_stream_bytes"] = inner.x_stream_bytes
         # what storing the rows in the precision's storage type cost (data/source.py): 0.0 = nothing
         rep["storage_max_rel_rounding"] = getattr(self.source, "storage_max_rel_rounding", None)
         if self.tx is not None and self.tx.name in P2P_TRANSPORTS:
@@ -786,7 +793,7 @@ class Trainer:
             return type(plan).__name__ if plan is not None else None
         if getattr(inner, "device", None) is not None and inner.device.type != "cuda":
             return "torch reference path (CPU)"
-        return inner.choice.label()
+        return inner.choice.label() + (", 58-bit rows" if getattr(inner, "packed", False) else "")
 
     def _master_loop_native(self, timed_start, log, start: int = 0) -> TrainResult:
         """Master rounds in csrc/runtime/master_pump.cpp (MasterPump); Python only keeps the books."""

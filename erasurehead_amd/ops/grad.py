@@ -42,6 +42,9 @@ N_CUS = 256  # MI355X compute units (8 XCDs x 32)
 # the headline, profiles/round2/s2_multi, round2/s2_epi); 2900 rows per CU (~742k rows) sits in between.
 LONG_STREAM_ROWS_PER_CU = 2900
 
+PACK58_ROW_BYTES = 7424  # csrc/kernels/pack58.h kRowBytes: a row of <= 1024 fp64 columns in 58 bits per value
+PACK58_WINDOW = 31       # binades a partition's exponent window holds
+
 KIND_IDS = {"fused": 0, "multi": 1, "staged": 2, "mfma": 3, "wide": 4, "twopass": -1}
 
 
@@ -161,6 +164,33 @@ def multi_bundle_rows(distinct_rows: int, fp32: bool = False, n_cus: int = N_CUS
     while not fits(rows) and rows < max(parts):
         rows += gran
     return rows if fits(rows) else base  # more partitions than slots: short bundles keep the tail short
+
+
+def pack_eligible(choice: KernelChoice, prec_code: int, ld: int, cpl: Optional[int]) -> bool:
+    """Plans that can stream the 58-bit copy of their rows (csrc/kernels/grad_dense_packed.hip): fp64 folded
+    one-wave bundles of 16 columns per lane."""
+    return (choice.kind == "multi" and choice.fold and not choice.pair and prec_code == 0 and cpl == 16
+            and 512 < ld <= 1024)
+
+
+def pack_auto(distinct_rows: int, n_cus: int = N_CUS) -> bool:
+    """Whether an eligible plan is packed by default: long streams (the rule of :func:`multi_slots`), where the
+    gradient is bound by the bytes of X.  (``--pack off`` / ``RunConfig.pack`` is the A/B switch: the Trainer
+    then asks for a plain plan.)"""
+    return distinct_rows >= LONG_STREAM_ROWS_PER_CU * n_cus
+
+
+def pack58_window(X: torch.Tensor, chunk_rows: int = 16384) -> int:
+    """The first biased exponent E0 of the 31-binade window that holds the most values of fp64 X."""
+    hist = torch.zeros(2048, dtype=torch.int64, device=X.device)
+    for r in range(0, X.shape[0], chunk_rows):
+        e = (X[r:r + chunk_rows].contiguous().view(torch.int64) >> 52) & 0x7FF
+        hist += torch.bincount(e.flatten(), minlength=2048)
+    h = hist.cpu().numpy()
+    h[0] = h[2047] = 0  # zeros need no window; denormals, inf and NaN have no encoding
+    c = np.concatenate([[0], np.cumsum(h)])
+    e0 = np.arange(1, 2046 - PACK58_WINDOW + 2)
+    return int(e0[np.argmax(c[e0 + PACK58_WINDOW] - c[e0])])
 
 
 def fill_splits(part_rows: Dict[int, int], wgs: int, per_wg: int = 4) -> Optional[Dict[int, List[int]]]:
@@ -450,8 +480,12 @@ class DenseGradPlan:
 
     def __init__(self, messages: Sequence[Sequence[Tuple[int, float]]],
                  partitions: Dict[int, Tuple[torch.Tensor, torch.Tensor]], prec: Precision, loss: int, d: int,
-                 target_tasks: Optional[int] = None, choice: Optional[KernelChoice] = None):
-        """choice: the kernel to launch (tests / sweeps); default: :func:`choose_kernel`'s measured pick."""
+                 target_tasks: Optional[int] = None, choice: Optional[KernelChoice] = None,
+                 pack: Optional[bool] = None, pack_e0: Optional[int] = None):
+        """choice: the kernel to launch (tests / sweeps); default: :func:`choose_kernel`'s measured pick.
+        pack: stream the 58-bit copy of the rows (:func:`pack_eligible`); default: :func:`pack_auto`'s rule,
+        True forces it on an eligible plan of any size (tests).  pack_e0: the exponent window of every
+        partition instead of the one that holds most of its values (tests)."""
         _reject_softmax(loss)
         self.prec = prec
         self.loss = loss
@@ -496,9 +530,49 @@ class DenseGradPlan:
         if self.bundle_rows:
             target_tasks = max(1, -(-self.total_rows // self.bundle_rows))
         self._run_launcher = None  # run()'s own launcher (native_launcher() hands out fresh ones)
+        self.packed = False
+        self.packed_bundles = self.plain_bundles = 0
+        self.x_stream_bytes = self.distinct_bytes
         if self.device.type == "cuda":
             self._native_choice = c.native()
             self._build_tables(target_tasks)
+            eligible = pack_eligible(c, prec.code, self.ld, self.cpl) and self.ntasks > 0
+            if pack and not eligible:
+                raise ValueError("packed rows need fp64 folded one-wave bundles of 16 columns per lane")
+            if eligible and (pack or (pack is None and pack_auto(distinct_rows) and self._pack_room())):
+                self._pack_rows(pack_e0)
+
+    # ---- 58-bit packed copy of the rows (csrc/kernels/pack58.h) --------------------------
+    def _pack_room(self) -> bool:
+        """Room in HBM for the second copy (the rule of Trainer._check_hbm)."""
+        rows = sum(self.partitions[p][0].shape[0] for p in set(self._seg_parts))
+        free, _ = torch.cuda.mem_get_info(self.device)
+        return rows * PACK58_ROW_BYTES <= 0.92 * free
+
+    def _pack_rows(self, e0: Optional[int]) -> None:
+        """Pack every distinct partition once; the packer flags the bundles whose copy is exact."""
+        dev = self.device
+        parts = sorted(set(self._seg_parts))
+        self.pack_e0 = {p: int(e0) if e0 is not None else pack58_window(self.partitions[p][0]) for p in parts}
+        copies = {p: torch.empty(self.partitions[p][0].shape[0] * PACK58_ROW_BYTES, dtype=torch.uint8, device=dev)
+                  for p in parts}
+        R = self.choice.replicas
+        flags = torch.zeros(self.ntasks // R, dtype=torch.int32, device=dev)
+        self._pack_args = ([copies[p] for p in self._seg_parts],
+                           [int(self.partitions[p][0].shape[0]) for p in self._seg_parts],
+                           torch.tensor([self.pack_e0[p] for p in self._seg_parts], dtype=torch.int32, device=dev), flags)
+        self._pack_done = False
+        self.packed = True
+        self._run_launcher = self.native_launcher()  # the first launcher of the plan runs the packer
+        lead = self.tasks.cpu().numpy().reshape(-1, R, 5)[:, 0, :]
+        live = lead[:, 1] >= 0
+        self.bundle_flags = flags.cpu().numpy().astype(bool) & live
+        nrows = (lead[:, 3] - lead[:, 2]).astype(np.int64)
+        self.packed_bundles = int(self.bundle_flags.sum())
+        self.plain_bundles = int((live & ~self.bundle_flags).sum())
+        es = torch.tensor([], dtype=self.prec.storage).element_size()
+        self.x_stream_bytes = int(nrows[self.bundle_flags].sum()) * PACK58_ROW_BYTES + \
+            int(nrows[live & ~self.bundle_flags].sum()) * self.ld * es
 
     # ---- device tables ----------------------------------------------------------------
     def _build_tables(self, target_tasks: int):
@@ -511,12 +585,14 @@ class DenseGradPlan:
             splits = fill_splits({p: self.partitions[p][0].shape[0] for m in self.messages for p, _ in m},
                                  self.choice.fill)
         seg_id = 0
+        self._seg_parts: List[int] = []  # the partition behind every segment
         keys = []  # (partition, first row) of every task: equal keys read identical rows
         for slot, m in enumerate(self.messages):
             for p, coef in m:
                 X, y = self.partitions[p]
                 n = X.shape[0]
                 segs += _SEG.pack(X.data_ptr(), y.data_ptr(), float(coef), n)
+                self._seg_parts.append(p)
                 # (fill_splits leaves out empty partitions: they get no task)
                 bounds = splits.get(p, [0]) if splits else list(range(0, n, rows_per_task)) + [n]
                 for r0, r1 in zip(bounds[:-1], bounds[1:]):
@@ -626,8 +702,12 @@ class DenseGradPlan:
             raise RuntimeError("native launchers need GPU tensors")
         C = native()
         if self.cpl is not None:
-            return C.GradLauncher.dense(self.prec.code, self.loss, self.cpl, self.segs, self.tasks, self.slab,
-                                        self.slot_task_begin, self.part, self.ld, choice=self._native_choice)
+            launcher = C.GradLauncher.dense(self.prec.code, self.loss, self.cpl, self.segs, self.tasks, self.slab,
+                                            self.slot_task_begin, self.part, self.ld, choice=self._native_choice)
+            if self.packed:
+                launcher.set_packed(*self._pack_args, pack=not self._pack_done)
+                self._pack_done = True
+            return launcher
         return C.GradLauncher.dense(self.prec.code, self.loss, 0, self.segs, self.tasks, self.slab,
                                     self.slot_task_begin, self.part, self.ld, self.task_row_off, self.rbuf)
 
