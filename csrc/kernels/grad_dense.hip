@@ -168,7 +168,8 @@ grad_dense_fused(const Segment* __restrict__ segs, const Task* __restrict__ task
 
 // ----- Replica bundles in ONE wave: each row is loaded once, into registers, and every replica
 // computes its own message from there. -----
-// Same bundle table as grad_dense_bundle (R task slots reading the same rows); one wave per bundle.
+// The bundle table: R task slots per bundle, all reading the same rows of one partition; slot 0 is always a real
+// task except in FOLD pad bundles, a slot past the bundle's replicas has seg < 0.  One wave per bundle.
 // The wave double-buffers whole rows in VGPRs (the next row's loads are in flight while the current
 // one is computed), so there is no LDS staging and no barrier.  Per row and per replica: its own
 // dot product against beta (every replica's chain starts from an opaque zero, so the compiler
@@ -441,8 +442,8 @@ grad_dense_multi(const Segment* __restrict__ segs, const Task* __restrict__ task
 }
 
 // ----- Replica bundles staged through LDS: one HBM read per row, one wave per replica. -----
-// Same task table as grad_dense_bundle (R slots per workgroup, all reading the same rows of one
-// partition).  The workgroup streams its row range through an NS-stage LDS ring with
+// The same bundle table, one bundle per workgroup: R task slots reading the same rows of one partition,
+// slot 0 always a real task.  The workgroup streams its row range through an NS-stage LDS ring with
 // global_load_lds (16-byte LDS-DMA, no staging registers): NS-1 stages are in flight while every
 // replica wave computes the oldest one from LDS — its own dot product against beta, residual with
 // its own coefficient, and gradient accumulation — and writes its own slab row.  The rows of a
@@ -1174,11 +1175,7 @@ static hipError_t launch_multi(bool fold, bool lane_epi, bool pair, dim3 grid, d
   } else if (lane_epi) {
     kern = grad_dense_multi<T, A, C, LOSS, R, true, 1>;
   }
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-  }
+  if (const hipError_t e = allow_dynamic_lds(kern, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, grid, block, lds, st, segs, tasks, nb, beta, slab, ld, gate, g_stamps);
   return hipGetLastError();
 }
@@ -1194,11 +1191,7 @@ static hipError_t launch_cpl(const Segment* segs, const Task* tasks, int ntasks,
     const int R = k.replicas;
     if (k.kind == kGradStaged) {  // rows streamed once through an LDS ring, one wave per replica
       auto kern = k.pair ? grad_dense_staged<T, A, C, LOSS, true> : grad_dense_staged<T, A, C, LOSS, false>;
-      if (sg.lds > 65536) {
-        const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sg.lds));
-        if (ea != hipSuccess) return ea;
-      }
+      if (const hipError_t e = allow_dynamic_lds(kern, sg.lds); e != hipSuccess) return e;
       hipLaunchKernelGGL(kern, dim3(ntasks / R), dim3(64 * R * sg.wpr), sg.lds, st, segs, tasks, beta, slab, ld,
                          sg.srows, sg.pieces, sg.nstage, sg.wpr, gate);
       return hipGetLastError();

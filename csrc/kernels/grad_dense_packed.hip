@@ -257,11 +257,7 @@ hipError_t launch_p58(bool lane_epi, int nb, hipStream_t st, const Segment* segs
                       double* slab, int ld, const int* gate, long long* stamps, const PackedRows& pk) {
   constexpr size_t lds = 3ull * R * 16 * kWave * sizeof(double);
   auto kern = lane_epi ? grad_dense_p58<LOSS, R, 1> : grad_dense_p58<LOSS, R, 0>;
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-  }
+  if (const hipError_t e = allow_dynamic_lds(kern, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(nb / 4), dim3(256), lds, st, segs, tasks, nb, beta, slab, ld, gate, stamps, pk);
   return hipGetLastError();
 }

@@ -30,6 +30,7 @@
 
 #include "common.h"
 #include "grad_dense.h"
+#include "launchers.h"
 #include "lds_dma.h"
 
 namespace eh {
@@ -552,18 +553,14 @@ hipError_t grad_mfma_launch(int loss, const Segment* segs, const Task* tasks, in
       auto kern = g_mfma_stream == 3 ? grad_vring_mfma<kL, 2> : grad_vring_mfma<kL, 3>;
       constexpr int vlds = 2 * (kMfNW * kVrPieces * 1024 + 256) + kMfNW * 16 * 32 * 4 + 16 * 32 * 2;
       static_assert(vlds <= 160 * 1024, "two stage buffers + partial Z + residuals");
-      const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, vlds);
-      if (ea != hipSuccess) return ea;
+      if (const hipError_t e = allow_dynamic_lds(kern, vlds); e != hipSuccess) return e;
       hipLaunchKernelGGL(kern, dim3(ntasks / R), dim3(64 * kMfNW), vlds, st, segs, tasks, beta, slab, ld, R, gate,
                          g_mfma_probe);
       return hipGetLastError();
     }
     auto kern = pack ? (rows == 32 ? grad_staged_mfma<kL, 32, true> : grad_staged_mfma<kL, 16, true>)
                      : (rows == 32 ? grad_staged_mfma<kL, 32, false> : grad_staged_mfma<kL, 16, false>);
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (ea != hipSuccess) return ea;
+    if (const hipError_t e = allow_dynamic_lds(kern, lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(ntasks / R), dim3(64 * kMfNW), lds, st, segs, tasks, beta, slab, ld, R, pieces,
                        nstage, gate, g_mfma_probe);
     return hipGetLastError();

@@ -226,11 +226,7 @@ static hipError_t launch_softmax(int C, const void* segs, const void* tasks, int
   const int srows = softmax_stage_rows(rowbytes);
   const size_t lds = softmax_lds_bytes(srows, rowbytes, sizeof(A));
   auto kern = grad_softmax<T, A, CPL>;
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-  }
+  if (const hipError_t e = allow_dynamic_lds(kern, lds); e != hipSuccess) return e;
   if (ntasks > 0)
     hipLaunchKernelGGL(kern, dim3(ntasks), dim3(64 * kSmWaves), lds, st, static_cast<const Segment*>(segs),
                        static_cast<const Task*>(tasks), static_cast<const A*>(beta), static_cast<A*>(slab), C, ld, srows,

@@ -788,14 +788,9 @@ hipError_t grad_sparse_launch(int dtype, int loss, const SparseArgs& a, const vo
       // (spreading covtype's 198k row pairs evenly over all 256 CUs instead of 194 full workgroups measured
       // 17.7 vs 17.0 us: the per-workgroup beta staging, not the CU count, sets the pace)
       const dim3 grid(static_cast<unsigned>(std::min<long long>(cus, ((a.nrows + 1) / 2 + 1023) / 1024)));
-      auto go = [&](const void* kern) -> hipError_t {
-        return blds > 64 * 1024 ? hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      static_cast<int>(blds))
-                                : hipSuccess;
-      };
 #define EH_ELLL(A_, L_, I_, V_)                                                                                  \
   {                                                                                                              \
-    const hipError_t e = go(reinterpret_cast<const void*>(ell_rows_lds<A_, L_, I_, V_>));                        \
+    const hipError_t e = allow_dynamic_lds(ell_rows_lds<A_, L_, I_, V_>, blds);                                  \
     if (e != hipSuccess) return e;                                                                               \
     hipLaunchKernelGGL((ell_rows_lds<A_, L_, I_, V_>), grid, dim3(1024), blds, st, a, (const A_*)beta, gate);   \
   }
@@ -852,10 +847,11 @@ hipError_t grad_sparse_launch(int dtype, int loss, const SparseArgs& a, const vo
     if (a.u_lds > (a.dst ? 2 : 1) * kStageRegs * 1024) return hipErrorInvalidValue;
     if (a.dst && (a.sub_begin || a.nspan || a.nempty)) return hipErrorInvalidValue;
     const dim3 grid(static_cast<unsigned>(a.nwg));
+    // csc_tiles_lds's static arrays (run_col, run_val, s_head, s_tail at fp64) next to the staged residuals
+    constexpr size_t kTilesStaticLds = kWgWaves * kRunCap * 12 + 2 * kMaxWgTiles * 8;
 #define EH_TLDS3(A_, R_, V_, L_, S_)                                                                            \
   {                                                                                                              \
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(csc_tiles_lds<A_, R_, V_, L_, S_>),    \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ulds));   \
+    const hipError_t e = allow_dynamic_lds(csc_tiles_lds<A_, R_, V_, L_, S_>, ulds, kTilesStaticLds);            \
     if (e != hipSuccess) return e;                                                                               \
     hipLaunchKernelGGL((csc_tiles_lds<A_, R_, V_, L_, S_>), grid, dim3(1024), ulds, st, a, gate);                 \
   }

@@ -22,6 +22,16 @@ namespace eh {
 bool strict_release();
 void set_release_form(bool strict);
 
+// A launch whose LDS exceeds 64 KiB has to be allowed per kernel first; at or below that there is nothing to do.
+// bytes: the launch's dynamic LDS; static_bytes: what the kernel declares besides (an upper bound will do).
+// Call right before the launch: `if (const hipError_t e = allow_dynamic_lds(kern, lds); e != hipSuccess) return e;`
+template <class K>
+inline hipError_t allow_dynamic_lds(K kern, size_t bytes, size_t static_bytes = 0) {
+  if (bytes + static_bytes <= 65536) return hipSuccess;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             static_cast<int>(bytes));
+}
+
 // ---- worker gradient (grad_dense.hip + slab_reduce.hip, grad_sparse.hip) ---------------
 // dtype: 0 fp64 storage/acc, 1 fp32/fp32, 2 bf16 storage/fp32 acc, 3 fp32 storage/fp64 acc; loss: 0 logistic,
 // 1 least squares

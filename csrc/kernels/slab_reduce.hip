@@ -328,11 +328,7 @@ hipError_t slab_reduce_update_launch(int dtype, const void* slab, const int* stb
     const size_t lds = static_cast<size_t>(nslots) * kWave * sizeof(A);
     hipLaunchKernelGGL(slab_reduce_partial<A>, dim3(ceil_div(ld, kWave), nslots, kSplits), dim3(256), 0, st,
                        static_cast<const A*>(slab), stb, static_cast<A*>(part), ld, nullptr);
-    if (lds > 60 * 1024) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(slab_final_update<A>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-      if (e != hipSuccess) return e;
-    }
+    if (const hipError_t e = allow_dynamic_lds(slab_final_update<A>, lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(slab_final_update<A>, dim3(ceil_div(ld, kWave)), dim3(1024), lds, st,
                        static_cast<const A*>(part), static_cast<A*>(G), ld, nslots, up);
     return hipGetLastError();
