@@ -168,6 +168,21 @@ hipError_t grad_softmax_launch(int dtype, int classes, const void* segs, const v
                                const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb,
                                int d_x, int ld_x, hipStream_t st, const int* gate = nullptr);
 
+// ---- several scalar-loss models in one pass (grad_multimodel.hip) ------------------------------
+// The softmax launch's contract for M independent models of one scalar loss (an (alpha, lr) sweep): beta
+// and every Gb row are model-major [models][ld_x], Gb[p] block k = gradient of partition p's loss sum at
+// beta block k with coefficient 1.  dtype 0 fp64 / 1 fp32 / 3 fp32 storage with fp64 accumulators (beta,
+// labels, slab and Gb in the accumulator type), loss 0..2, 2 <= models <= 8, ld_x <= 1024 and a multiple
+// of the storage type's 16-byte vector; anything else returns hipErrorInvalidValue and launches nothing.
+// segs / tasks / part_task_begin / slab [ntasks][kModelsSubs][models * ld_x] as for grad_softmax_launch.
+constexpr int kModelsSubs = 4;
+constexpr int kModelsMin = 2;
+constexpr int kModelsMax = 8;
+constexpr int kModelsMaxLd = 1024;
+hipError_t grad_models_launch(int dtype, int loss, int models, const void* segs, const void* tasks, int ntasks,
+                              const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb, int d_x,
+                              int ld_x, hipStream_t st, const int* gate = nullptr);
+
 // layout probes of the bf16 MFMA gradient (grad_mfma.hip): one 16x16x32 product; one transposing read
 hipError_t mfma_probe_launch(const float* A, const float* B, float* C, hipStream_t st);
 hipError_t tr_probe_launch(const float* tile, int rowlen, float* out, hipStream_t st);
@@ -223,6 +238,18 @@ hipError_t combine_update_launch(const CombineArgs& args, int msg_dtype, int w_d
                                  double* g_out, int d, int ld, double decay, double gm,
                                  double l2, double theta, int rule, hipStream_t st,
                                  long long* stamp = nullptr);
+// The same combine + update for a model of several blocks with their own coefficients (a multi-model run,
+// grad_multimodel.hip): the vector is [nblocks][block_ld], column c takes decay / gm / l2 of block
+// c / block_ld and is padding when c % block_ld >= d_x (beta stays exactly zero there, beta_w gets zero);
+// theta and the rule are common.  Block k's output is bitwise combine_update's on that block alone.
+constexpr int kMaxBlocks = 8;
+struct BlockCoefs {
+  int nblocks, block_ld, d_x;
+  double decay[kMaxBlocks], gm[kMaxBlocks], l2[kMaxBlocks];
+};
+hipError_t combine_update_blocks_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* u,
+                                        double* hist, void* beta_w, double* g_out, const BlockCoefs& bc, double theta,
+                                        int rule, hipStream_t st, long long* stamp = nullptr);
 // one device timestamp (wall_clock64, hipDeviceAttributeWallClockRate kHz) into *out
 hipError_t stamp_launch(long long* out, hipStream_t st);
 

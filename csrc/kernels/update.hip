@@ -62,6 +62,74 @@ combine_update(const CombineArgs args, double* __restrict__ beta, double* __rest
   if (g_out) g_out[c] = g;
 }
 
+// combine_update for a model of several blocks with per-block coefficients (launchers.h BlockCoefs): the
+// same batched message loads, the same fma chain and the same update expressions, so block k is bitwise
+// what combine_update gives on that block alone with (decay_k, gm_k, l2_k).
+template <typename M, typename W>
+__global__ void __launch_bounds__(256)
+combine_update_blocks(const CombineArgs args, const BlockCoefs bc, double* __restrict__ beta, double* __restrict__ u,
+                      double* __restrict__ hist, W* __restrict__ beta_w, double* __restrict__ g_out, double theta,
+                      int rule, long long* __restrict__ stamp) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (stamp && c == 0) *stamp = wall_clock64();
+  if (c >= bc.nblocks * bc.block_ld) return;
+  const int blk = c / bc.block_ld;
+  if (c - blk * bc.block_ld >= bc.d_x) {  // padded columns of every block stay exactly zero
+    if (beta_w) beta_w[c] = W(0);
+    return;
+  }
+  double decay = bc.decay[0], gm = bc.gm[0], l2 = bc.l2[0];
+#pragma unroll
+  for (int k = 1; k < kMaxBlocks; ++k)  // selects, not a dynamically indexed copy of the argument
+    if (k == blk) {
+      decay = bc.decay[k];
+      gm = bc.gm[k];
+      l2 = bc.l2[k];
+    }
+  double g = 0.0;
+  constexpr int kBatch = 8;
+  for (int m0 = 0; m0 < args.nmsg; m0 += kBatch) {
+    double v[kBatch];
+#pragma unroll
+    for (int k = 0; k < kBatch; ++k)
+      v[k] = m0 + k < args.nmsg ? static_cast<double>(static_cast<const M*>(args.msg[m0 + k])[c]) : 0.0;
+#pragma unroll
+    for (int k = 0; k < kBatch; ++k)
+      if (m0 + k < args.nmsg) g = fma(args.coef[m0 + k], v[k], g);
+  }
+  const double b = beta[c];
+  double nb;
+  if (rule == 0) {  // GD
+    nb = decay * b - gm * g;
+  } else {  // AGD
+    const double yt = (1.0 - theta) * b + theta * u[c];
+    nb = yt - gm * g - l2 * b;
+    u[c] = b + (nb - b) * (1.0 / theta);
+  }
+  beta[c] = nb;
+  if (hist) hist[c] = nb;
+  if (beta_w) beta_w[c] = static_cast<W>(nb);
+  if (g_out) g_out[c] = g;
+}
+
+hipError_t combine_update_blocks_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* u,
+                                        double* hist, void* beta_w, double* g_out, const BlockCoefs& bc, double theta,
+                                        int rule, hipStream_t st, long long* stamp) {
+  if (bc.nblocks < 1 || bc.nblocks > kMaxBlocks || bc.block_ld < 1 || bc.d_x < 1 || bc.d_x > bc.block_ld ||
+      (msg_dtype != 0 && msg_dtype != 1) || (w_dtype != 0 && w_dtype != 1))
+    return hipErrorInvalidValue;
+  const dim3 block(256), grid(ceil_div(bc.nblocks * bc.block_ld, 256));
+  if (msg_dtype == 0 && w_dtype == 0)
+    hipLaunchKernelGGL((combine_update_blocks<double, double>), grid, block, 0, st, args, bc, beta, u, hist, (double*)beta_w, g_out, theta, rule, stamp);
+  else if (msg_dtype == 0 && w_dtype == 1)
+    hipLaunchKernelGGL((combine_update_blocks<double, float>), grid, block, 0, st, args, bc, beta, u, hist, (float*)beta_w, g_out, theta, rule, stamp);
+  else if (msg_dtype == 1 && w_dtype == 0)
+    hipLaunchKernelGGL((combine_update_blocks<float, double>), grid, block, 0, st, args, bc, beta, u, hist, (double*)beta_w, g_out, theta, rule, stamp);
+  else
+    hipLaunchKernelGGL((combine_update_blocks<float, float>), grid, block, 0, st, args, bc, beta, u, hist, (float*)beta_w, g_out, theta, rule, stamp);
+  return hipGetLastError();
+}
+
 // msg dtype: 0 fp64, 1 fp32; worker beta dtype: 0 fp64, 1 fp32
 hipError_t combine_update_launch(const CombineArgs& args, int msg_dtype, int w_dtype,
                                  double* beta, double* u, double* hist, void* beta_w,

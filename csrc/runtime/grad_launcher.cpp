@@ -104,6 +104,59 @@ std::shared_ptr<GradLauncher> make_softmax(int64_t dtype, int64_t classes, const
   return g;
 }
 
+// Multi-model plan (ops/multimodel.py MultiModelGradPlan): softmax's layout for `models` independent models of
+// one scalar loss; rows of models * ld_x elements, the device encoding forms the messages unless they are
+// exactly the partitions.
+std::shared_ptr<GradLauncher> make_multimodel(int64_t dtype, int64_t loss, int64_t models, const Tensor& segs,
+                                              const Tensor& tasks, const Tensor& slab, const Tensor& part_task_begin,
+                                              int64_t d_x, int64_t ld_x) {
+  for (auto* t : {&segs, &tasks, &slab, &part_task_begin}) need_gpu(*t, "multi-model plan operand");
+  need(dtype == 0 || dtype == 1 || dtype == 3, "multi-model: fp64, fp32 or fp32x64 (fp32 storage, fp64 accumulators)");
+  need(loss >= 0 && loss <= 2, "multi-model: logistic, least squares or squared hinge");
+  need(models >= eh::kModelsMin && models <= eh::kModelsMax, "multi-model: models must be in 2..8");
+  need(ld_x >= 1 && ld_x <= eh::kModelsMaxLd && d_x >= 1 && d_x <= ld_x && ld_x % eh::storage_vec((int)dtype) == 0,
+       "multi-model: rows of at most 1024 columns, padded to the 16-byte vector width");
+  need(tasks.dim() == 2 && tasks.size(1) == 5 && tasks.scalar_type() == at::kInt, "tasks must be int32 [n,5]");
+  need(segs.scalar_type() == at::kByte && segs.numel() % 32 == 0, "segs must be packed uint8 [nseg*32]");
+  need(part_task_begin.scalar_type() == at::kInt && part_task_begin.numel() >= 1, "part_task_begin must be int32");
+  auto g = std::make_shared<GradLauncher>();
+  g->kind = 4;
+  g->dtype = (int)dtype;
+  g->acc = eh::storage_acc_code((int)dtype);
+  g->loss = (int)loss;
+  g->classes = (int)models;
+  g->d_x = (int)d_x;
+  g->ld_x = (int)ld_x;
+  g->ld = (int)(models * ld_x);
+  g->ntasks = (int)tasks.size(0);
+  g->nparts = (int)part_task_begin.numel() - 1;
+  g->nslots = g->rows = g->nparts;
+  need(acc_code(slab) == g->acc &&
+           slab.numel() >= (int64_t)std::max(1, g->ntasks) * eh::kModelsSubs * g->ld,
+       "slab must hold [ntasks][4][models * ld_x] partial sums (acc dtype)");
+  {  // the kernel indexes segments, rows and slab rows with the task table: checked once, on the host
+    const Tensor tc = tasks.cpu().contiguous(), pc = part_task_begin.cpu().contiguous(), sc = segs.cpu().contiguous();
+    const int* T = tc.data_ptr<int>();
+    const int* P = pc.data_ptr<int>();
+    const auto* S = reinterpret_cast<const eh::Segment*>(sc.data_ptr<uint8_t>());
+    const int64_t nseg = segs.numel() / 32;
+    for (int k = 0; k < g->ntasks; ++k) {
+      const eh::Task& t = reinterpret_cast<const eh::Task*>(T)[k];
+      need(t.seg >= 0 && t.seg < nseg && t.row_begin >= 0 && t.row_begin <= t.row_end &&
+               t.row_end <= S[t.seg].nrows && t.slab >= 0 && t.slab < std::max(1, g->ntasks),
+           "tasks: (slot, segment, row_begin <= row_end <= the segment's rows, slab row) inside the tables");
+    }
+    need(P[0] == 0 && P[g->nparts] == g->ntasks, "part_task_begin: [0, .., ntasks]");
+    for (int p = 0; p < g->nparts; ++p) need(P[p] <= P[p + 1], "part_task_begin: non-decreasing");
+  }
+  g->segs = segs.data_ptr();
+  g->tasks = tasks.data_ptr();
+  g->slab = slab.data_ptr();
+  g->stb = part_task_begin.data_ptr<int>();
+  g->keep = {segs, tasks, slab, part_task_begin};
+  return g;
+}
+
 // Sparse plan (ops/grad.py SparseGradPlan): every distinct local partition once; the plan's device
 // encoding (set_encode) forms the messages.  Tensors are kept alive by the launcher.
 std::shared_ptr<GradLauncher> make_sparse(int64_t loss, const Tensor& y, const Tensor& u, std::optional<Tensor> ell_idx,
@@ -295,6 +348,8 @@ void bind_grad_launcher(py::module& m) {
                   py::arg("choice") = eh::KernelChoice{})
       .def_static("softmax", &make_softmax, py::arg("dtype"), py::arg("classes"), py::arg("segs"), py::arg("tasks"),
                   py::arg("slab"), py::arg("part_task_begin"), py::arg("d_x"), py::arg("ld_x"))
+      .def_static("multimodel", &make_multimodel, py::arg("dtype"), py::arg("loss"), py::arg("models"), py::arg("segs"),
+                  py::arg("tasks"), py::arg("slab"), py::arg("part_task_begin"), py::arg("d_x"), py::arg("ld_x"))
       .def_static("sparse", &make_sparse, py::arg("loss"), py::arg("y"), py::arg("u"), py::arg("ell_idx"), py::arg("lo"),
                   py::arg("row_ptr"), py::arg("col_idx"), py::arg("vals"), py::arg("crow"), py::arg("cvals"),
                   py::arg("col_ptr"), py::arg("tiles"), py::arg("part_entry0"), py::arg("part_row0"),

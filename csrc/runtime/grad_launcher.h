@@ -1,6 +1,6 @@
 // GradLauncher: the per-round gradient launch of one rank's local messages, captured once from the
 // Python plan (ops/grad.py, ops/softmax.py) by the one validator of its kind (grad_launcher.cpp
-// make_dense / make_softmax / make_sparse).  The plan object keeps every referenced tensor alive; the
+// make_dense / make_softmax / make_multimodel / make_sparse).  The plan object keeps every referenced tensor alive; the
 // launcher also holds references.  The launch functions are inline: the pumps call them every round.
 #pragma once
 
@@ -15,7 +15,7 @@
 namespace eh {
 
 struct GradLauncher {
-  int kind = 0;  // 0 dense fused, 1 dense two-pass, 2 sparse, 3 multi-class softmax
+  int kind = 0;  // 0 dense fused, 1 dense two-pass, 2 sparse, 3 multi-class softmax, 4 several scalar-loss models
   int dtype = 0, loss = 0, cpl = 0, ntasks = 0, nslots = 0, ld = 0;
   KernelChoice choice{};
   const void* segs = nullptr;
@@ -30,6 +30,7 @@ struct GradLauncher {
   SparseArgs sa{};  // kind 2 (grad_sparse.hip); Gb is the launch's output
   // kind 3 (grad_softmax.hip): classes, data columns / row stride (ld is the flattened classes * ld_x),
   // distinct partitions (the rows the kernel writes) and their task ranges stb [nparts + 1]
+  // kind 4 (grad_multimodel.hip): the same layout with `classes` models of the scalar loss `loss`
   int classes = 0, d_x = 0, ld_x = 0, nparts = 0;
   // optional device encoding (csrc/kernels/encode.hip): the kernels above write the distinct
   // partitions' gradients into Gb, then G[slot] = sum_k coef * Gb[idx] for the enc_slots messages
@@ -102,6 +103,9 @@ struct GradLauncher {
       case 3:
         return grad_softmax_launch(dtype, classes, segs, tasks, ntasks, stb, nparts, beta, slab, G, d_x, ld_x, st,
                                    gate);
+      case 4:
+        return grad_models_launch(dtype, loss, classes, segs, tasks, ntasks, stb, nparts, beta, slab, G, d_x, ld_x, st,
+                                  gate);
       default:
         return hipErrorInvalidValue;
     }

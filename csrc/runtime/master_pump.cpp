@@ -251,6 +251,25 @@ class MasterPump {
     drain_ = drain;
   }
 
+  // Multi-model run (kernels/grad_multimodel.hip): the model is M blocks of block_ld columns (d_x of them data)
+  // and block k of round i takes decay / gm / l2 [i * M + k]; theta and the rule stay set_schedule's.  From
+  // then on combine() launches combine_update_blocks, and the rounds cannot run on the device arbiter.
+  void set_block_schedule(int M, int block_ld, int d_x, const std::vector<double>& decay, const std::vector<double>& gm,
+                          const std::vector<double>& l2) {
+    arb_ready_ = false;
+    need(M >= 2 && M <= eh::kMaxBlocks, "block schedule: 2..8 models");
+    need(block_ld >= 1 && d_x >= 1 && d_x <= block_ld && static_cast<int64_t>(M) * block_ld == ld_ && d_ == ld_,
+         "block schedule: models * block_ld must be the model length");
+    const size_t n = static_cast<size_t>(R_) * M;
+    need(decay.size() >= n && gm.size() >= n && l2.size() >= n, "block schedule arrays must be [R * models]");
+    blocks_ = M;
+    block_ld_ = block_ld;
+    block_dx_ = d_x;
+    bdecay_ = decay;
+    bgm_ = gm;
+    bl2_ = l2;
+  }
+
   // --delay-on worker: virtual delays the collector applies to REMOTE messages (the worker ranks
   // are physically late themselves); default: the same table as the local messages.
   void set_remote_delays(const std::vector<double>& delays) {
@@ -578,6 +597,7 @@ class MasterPump {
 
   // Why rounds [a, b) cannot run on the device arbiter ("" = they can).
   std::string device_blocker(int a, int b) const {
+    if (blocks_) return "per-model update coefficients (multi-model run)";
     if (comm_) return "messages travel over " + comm_->kind() + " (the arbiter polls IPC counters)";
     if (remote_.empty() || arb_src_.empty()) return "no remote workers";
     if ((int)arb_src_.size() > eh::kArbMaxSrc) return "more than 64 worker ranks";
@@ -811,11 +831,28 @@ class MasterPump {
       if (!ev.second) ev.second = make_event(hipEventDefault);
       record_timed(ev.first, stream_);
     }
-    hcheck(eh::combine_update_launch(a, acc_, acc_, beta_.data_ptr<double>(), u_.data_ptr<double>(),
-                                     hist_.data_ptr<double>() + static_cast<int64_t>(i) * ld_,
-                                     beta_row(i + 1), nullptr, d_, ld_, decay_[i], gm_[i],
-                                     l2_[i], theta_[i], update_rule_, stream_, stamp),
-           "combine_update");
+    if (blocks_) {
+      eh::BlockCoefs bc{};
+      bc.nblocks = blocks_;
+      bc.block_ld = block_ld_;
+      bc.d_x = block_dx_;
+      for (int k = 0; k < blocks_; ++k) {
+        const size_t j = static_cast<size_t>(i) * blocks_ + k;
+        bc.decay[k] = bdecay_[j];
+        bc.gm[k] = bgm_[j];
+        bc.l2[k] = bl2_[j];
+      }
+      hcheck(eh::combine_update_blocks_launch(a, acc_, acc_, beta_.data_ptr<double>(), u_.data_ptr<double>(),
+                                              hist_.data_ptr<double>() + static_cast<int64_t>(i) * ld_, beta_row(i + 1),
+                                              nullptr, bc, theta_[i], update_rule_, stream_, stamp),
+             "combine_update_blocks");
+    } else {
+      hcheck(eh::combine_update_launch(a, acc_, acc_, beta_.data_ptr<double>(), u_.data_ptr<double>(),
+                                       hist_.data_ptr<double>() + static_cast<int64_t>(i) * ld_,
+                                       beta_row(i + 1), nullptr, d_, ld_, decay_[i], gm_[i],
+                                       l2_[i], theta_[i], update_rule_, stream_, stamp),
+             "combine_update");
+    }
     if (events) hcheck(hipEventRecord(ev.second, stream_), "hipEventRecord");
   }
 
@@ -1094,6 +1131,8 @@ class MasterPump {
   std::vector<Tensor> arb_keep_;
   Tensor arb_log_, arb_tlog_, arb_abort_, arb_checks_;
   std::vector<double> decay_, gm_, l2_, theta_, delays_, remote_delays_;
+  int blocks_ = 0, block_ld_ = 0, block_dx_ = 0;  // set_block_schedule: per-model coefficients [R * blocks_]
+  std::vector<double> bdecay_, bgm_, bl2_;
   int repeat_ = 1;
   int update_rule_ = 0, stop_rule_ = 0, k_ = 0;
   bool drain_ = false;
@@ -1149,6 +1188,7 @@ void bind_master_pump(py::module& m) {
       .def("run_device", &MasterPump::run_device, py::arg("a"), py::arg("b"), py::arg("deadline_s"))
       .def("device_log", &MasterPump::device_log)
       .def("set_schedule", &MasterPump::set_schedule)
+      .def("set_block_schedule", &MasterPump::set_block_schedule)
       .def("set_decode", &MasterPump::set_decode)
       .def("add_table", &MasterPump::add_table)
       .def("begin", &MasterPump::begin, py::call_guard<py::gil_scoped_release>())

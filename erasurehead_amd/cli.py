@@ -41,6 +41,11 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--lr-t0", type=float, default=90.0)
     g.add_argument("--lr-decay", type=float, default=0.98)
     g.add_argument("--alpha", type=float, default=None)
+    g.add_argument("--alphas", type=parse_float_list, default=None, metavar="A1,A2,...",
+                   help="sweep: train one model per L2 strength in the same run (2..8 models, one pass over X per "
+                        "round); zipped with --lrs, a single value is broadcast")
+    g.add_argument("--lrs", type=parse_float_list, default=None, metavar="L1,L2,...",
+                   help="sweep: one model per learning rate (zipped with --alphas; not with an explicit lr_schedule)")
     g.add_argument("--seed", type=int, default=None)
     g.add_argument("--data", default="files", choices=["files", "synthetic"])
     g.add_argument("--data-seed", type=int, default=0)
@@ -98,6 +103,11 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+def parse_float_list(text: str) -> List[float]:
+    """'1e-4,1e-3' -> [0.0001, 0.001]."""
+    return [float(x) for x in str(text).split(",") if x.strip()]
+
+
 def parse_slow_ranks(items) -> dict:
     """['3:4', '5:2'] -> {3: 4, 5: 2}."""
     out = {}
@@ -126,7 +136,8 @@ def parse(argv: List[str]):
                     transport=a.transport, share_partitions=a.share_partitions, pack=a.pack, device_loop=a.device_loop,
                     tie_break=a.tie_break, tie_seed=a.tie_seed, shard=a.shard,
                     integrity=not a.no_integrity, delay_on=a.delay_on, slow_ranks=parse_slow_ranks(a.slow_ranks),
-                    dedicated_master=a.dedicated_master, device_records=a.device_records)
+                    dedicated_master=a.dedicated_master, device_records=a.device_records,
+                    sweep_alpha=a.alphas, sweep_lr=a.lrs)
     return cfg, a
 
 

@@ -11,10 +11,13 @@ defaults reproduce the reference, including its quirks, unl
 """
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
+
+SWEEP_MIN_MODELS, SWEEP_MAX_MODELS = 2, 8  # csrc/kernels/launchers.h kModelsMin / kModelsMax
 
 
 @dataclass
@@ -46,6 +49,10 @@ class RunConfig:
     precision: str = "fp64"  # fp64 | fp32 | bf16 | fp32x64 worker compute (master state always fp64)
     loss: str = "auto"  # auto (reference dispatch) | logistic | least_squares | squared_hinge | softmax
     classes: Optional[int] = None  # softmax only: number of classes, 2..8 (default 2)
+    # (alpha, lr) sweep: M = 2..8 models trained in one run from one pass over X per round (ops/multimodel.py).
+    # The lists are zipped; an absent list or one of length 1 is broadcast (absent: the run's alpha / lr).
+    sweep_alpha: Optional[List[float]] = None
+    sweep_lr: Optional[List[float]] = None
     seed: Optional[int] = None  # beta_0 / B matrix seed (reference: unseeded)
     data: str = "files"  # files | synthetic (on-device generator, no files)
     data_seed: int = 0
@@ -125,6 +132,38 @@ class RunConfig:
             raise ValueError(f"classes is an option of the softmax loss, not of {self.loss!r}")
         if any(int(f) < 1 for f in self.slow_ranks.values()):
             raise ValueError("slow rank factors must be integers >= 1")
+        self.sweep()  # the sweep's limits, each a ValueError that names it
+
+    def sweep(self) -> Optional[List[Tuple[float, float]]]:
+        """The (alpha_k, lr_k) of every model of a sweep run, or None without --alphas / --lrs."""
+        if self.sweep_alpha is None and self.sweep_lr is None:
+            return None
+        al = [float(a) for a in (self.sweep_alpha if self.sweep_alpha is not None else [self.alpha_value])]
+        lr = [float(x) for x in (self.sweep_lr if self.sweep_lr is not None else [self.lr])]
+        if not al or not lr:
+            raise ValueError("sweep: --alphas / --lrs must not be empty")
+        if len(al) > 1 and len(lr) > 1 and len(al) != len(lr):
+            raise ValueError(f"sweep: {len(al)} alphas and {len(lr)} lrs: lists longer than 1 must have equal lengths")
+        M = max(len(al), len(lr))
+        if not SWEEP_MIN_MODELS <= M <= SWEEP_MAX_MODELS:
+            raise ValueError(f"sweep: {M} models; a sweep trains {SWEEP_MIN_MODELS}..{SWEEP_MAX_MODELS} models "
+                             f"(give {SWEEP_MIN_MODELS} to {SWEEP_MAX_MODELS} values in --alphas or --lrs)")
+        if self.sweep_lr is not None and self.lr_schedule is not None:
+            raise ValueError("sweep: --lrs cannot be combined with an explicit lr_schedule (one list of step sizes)")
+        if self.loss == "softmax":
+            raise ValueError("sweep: --loss softmax is not supported with --alphas / --lrs "
+                             "(logistic, least_squares, squared_hinge or auto)")
+        al = al * M if len(al) == 1 else al
+        lr = lr * M if len(lr) == 1 else lr
+        return list(zip(al, lr))
+
+    def sweep_etas(self) -> Optional[np.ndarray]:
+        """[M, num_itrs]: model k's step schedule, eta() evaluated with lr = lr_k."""
+        sw = self.sweep()
+        if sw is None:
+            return None
+        return np.stack([dataclasses.replace(self, lr=lr, sweep_alpha=None, sweep_lr=None).eta()[: self.num_itrs]
+                         for _, lr in sw])
 
     @property
     def tie_seed_value(self) -> int:

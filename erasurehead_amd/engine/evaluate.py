@@ -7,6 +7,9 @@ Reference quirks reproduced unless ``fix_quirks``:
   * result names follow each scheme's (colliding) prefixes (codes/schemes.py).
 Squared-hinge runs (not in the reference) are scored and printed like logistic ones, and every result
 name carries the prefix ``sqhinge_`` so a run in the same data directory keeps the logistic files.
+Sweep runs (--alphas / --lrs, M models) are scored per model: the arrays get a trailing model axis [R, M], the
+console prints ``>> Model k: alpha = ..., lr = ...`` before model k's usual iteration lines, and model k's
+result names carry the prefix ``sweep{k}_`` (before ``sqhinge_`` where that applies).
 Softmax runs are scored by cross-entropy and accuracy: the console line carries the accuracy where the
 logistic line has the AUC, ``EvalResult.auc`` (and the ``auc`` result file) hold the accuracy, and the
 result names carry the prefix ``softmax_``.
@@ -38,7 +41,8 @@ class EvalResult:
     auc: np.ndarray  # softmax runs: the test accuracy of every round
     n_train: int
     n_test: int
-    files: Optional[Dict[str, str]] = None
+    files: Optional[Dict[str, str]] = None  # sweep runs: {"sweep{k}_" + key: path} of every model
+    best: Optional[int] = None  # sweep runs (arrays [R, M]): the model with the lowest final test loss
 
 
 def eval_partitions(trainer: Trainer):
@@ -114,10 +118,66 @@ def _evaluate_softmax(trainer: Trainer, res: TrainResult, log, write: bool) -> E
     return EvalResult(training_loss, testing_loss, acc, n_train, n_test, files)
 
 
+def sweep_prefix(k: int) -> str:
+    return f"sweep{k}_"
+
+
+def _evaluate_sweep(trainer: Trainer, res: TrainResult, log, write: bool) -> EvalResult:
+    """Every model of a sweep run through the single-model evaluation: betaset [R, M * ld_x] as R * M models."""
+    cfg, dev, prec = trainer.cfg, trainer.env.device, trainer.prec
+    M, d_x, ld_x, kind = trainer.models, trainer.d_x, trainer.ld_x, trainer.loss
+    R = res.betaset.shape[0]
+    B = torch.from_numpy(np.ascontiguousarray(res.betaset)).to(dev).reshape(R * M, ld_x)
+    parts = eval_partitions(trainer)
+    if cfg.verbose:
+        log(report.total_time_line(res.total_time))
+        if trainer.scheme.logs_eval_loading and not trainer.source.is_sparse:
+            for p in parts:
+                log(">> Loaded %d" % (p + 1))
+    sums, n_train = loss_sums(_train_chunks(trainer, parts, prec, dev), B, d_x, kind, acc=prec)
+    Xt, yt = trainer.source.test(prec, dev)
+    P, tsum = predictions_and_loss(Xt, yt, B, d_x, kind, acc=prec)
+    n_test = Xt.shape[0]
+    training_loss = (np.asarray(sums) / max(1, n_train)).reshape(R, M)
+    testing_loss = (np.asarray(tsum) / max(1, n_test)).reshape(R, M)
+    classify = is_classification(kind)
+    auc = (auc_columns(yt, P) if classify else np.zeros(R * M)).reshape(R, M)
+    files = None
+    do_write = write and (classify or cfg.save_linear)
+    if do_write:
+        files = {}
+        data_dir = getattr(trainer.source, "data_dir", None) or cfg.input_dir
+    for k in range(M):
+        if cfg.verbose:
+            log(">> Model %d: alpha = %g, lr = %g" % (k, trainer.sweep_alpha[k], trainer.sweep_lr[k]))
+            for i in range(R):
+                if classify:
+                    log(report.logistic_line(i, training_loss[i, k], testing_loss[i, k], auc[i, k], res.timeset[i]))
+                else:
+                    log(report.linear_line(i, training_loss[i, k], testing_loss[i, k], res.timeset[i]))
+        if do_write:
+            names = trainer.scheme.output_names(cfg.fix_quirks)
+            if kind == SQUARED_HINGE:
+                names = {key: SQHINGE_PREFIX + v for key, v in names.items()}
+            names = {key: sweep_prefix(k) + v for key, v in names.items()}
+            out = report.write_results(dio.results_dir(data_dir), names, training_loss[:, k], testing_loss[:, k],
+                                       auc[:, k], res.timeset, res.worker_timeset, cfg.full_precision_outputs)
+            files.update({sweep_prefix(k) + key: v for key, v in out.items()})
+    final = testing_loss[-1] if R else np.zeros(M)
+    best = int(np.argmin(np.where(np.isfinite(final), final, np.inf)))
+    if cfg.verbose:
+        log(">> Best model: %d (alpha = %g, lr = %g, final test loss %g)"
+            % (best, trainer.sweep_alpha[best], trainer.sweep_lr[best], final[best]))
+        log(">>> Done")
+    return EvalResult(training_loss, testing_loss, auc, n_train, n_test, files, best)
+
+
 def evaluate(trainer: Trainer, res: TrainResult, log=None, write: bool = True) -> EvalResult:
     log = log or report.log
     if is_multiclass(trainer.loss):
         return _evaluate_softmax(trainer, res, log, write)
+    if getattr(trainer, "models", 1) > 1:
+        return _evaluate_sweep(trainer, res, log, write)
     cfg = trainer.cfg
     dev = trainer.env.device
     prec = trainer.prec

@@ -54,8 +54,9 @@ from ..models.losses import (LEAST_SQUARES, LOGISTIC, LOSS_CHOICES, SOFTMAX, Upd
                              is_classification)
 from ..ops.grad import DenseGradPlan, SharedGradPlan, SparseGradPlan
 from ..ops.softmax import SoftmaxGradPlan
+from ..ops.multimodel import MultiModelGradPlan
 from ..ops.precision import get_precision
-from ..ops.update import combine_update
+from ..ops.update import combine_update, combine_update_blocks
 from ..parallel.collector import ArrivalCollector
 from ..parallel.dist import DistEnv
 from ..parallel.placement import make_shards, place_spread, place_units
@@ -178,6 +179,11 @@ class Trainer:
             self.loss = LOSS_CHOICES[cfg.loss]
         # multi-class softmax: the model is [classes][ld_x] flattened (ops/softmax.py); 1 for every other loss
         self.classes = check_classes(cfg.classes or 2) if self.loss == SOFTMAX else 1
+        # (alpha, lr) sweep: M models of one scalar loss, the model [M][ld_x] flattened (ops/multimodel.py)
+        sweep = cfg.sweep()
+        self.models = len(sweep) if sweep else 1
+        self.sweep_alpha = [a for a, _ in sweep] if sweep else None
+        self.sweep_lr = [x for _, x in sweep] if sweep else None
         self.rule_kind, self.rule_k = scheme.rule()
         self.update = UpdateRule("AGD" if scheme.fixed_agd else cfg.update_rule, cfg.alpha_value, cfg.n_rows,
                                  scheme.grad_scale())
@@ -250,6 +256,10 @@ class Trainer:
         if self.loss == SOFTMAX:
             self.d = self.ld = self.classes * self.ld_x
             SoftmaxGradPlan.check_supported(self.prec, self.classes, source.is_sparse)  # before any load
+        if self.models > 1:
+            self.d = self.ld = self.models * self.ld_x
+            MultiModelGradPlan.check_supported(self.prec, self.loss, self.models, source.is_sparse, self.ld_x,
+                                               bool(self.env.gpu))  # before any load
         dev = self.env.device
         needed = sorted({p for m in self.local_msgs for p, _ in m.segments})
         if not source.is_sparse and self.env.gpu:
@@ -262,6 +272,8 @@ class Trainer:
         def make_plan(messages):
             if self.loss == SOFTMAX:  # shares the distinct partitions by itself: --share-partitions changes nothing
                 return SoftmaxGradPlan(messages, parts, self.prec, self.classes, self.d_x)
+            if self.models > 1:  # likewise: every distinct partition once, whatever --share-partitions says
+                return MultiModelGradPlan(messages, parts, self.prec, self.loss, self.models, self.d_x)
             if source.is_sparse:
                 return SparseGradPlan(messages, parts, self.prec, self.loss, self.d, device=dev)
             kw = {"target_tasks": cfg.tasks} if cfg.tasks else {}
@@ -269,7 +281,7 @@ class Trainer:
                 kw["pack"] = False
             return DenseGradPlan(messages, parts, self.prec, self.loss, self.d, **kw)
 
-        share = cfg.share_partitions and self.loss != SOFTMAX
+        share = cfg.share_partitions and self.loss != SOFTMAX and self.models == 1
         if share and SharedGradPlan.worthwhile(segs, lambda p: parts[p][0].shape[0]):
             self.plan = SharedGradPlan(segs, make_plan)
         else:
@@ -373,7 +385,7 @@ class Trainer:
         counts = collections.Counter(p for m in self.local_msgs for p, _ in m.segments)
         if not counts or max(counts.values()) < 2:
             return "none"
-        if isinstance(plan, (SharedGradPlan, SparseGradPlan, SoftmaxGradPlan)):
+        if isinstance(plan, (SharedGradPlan, SparseGradPlan, SoftmaxGradPlan, MultiModelGradPlan)):
             return "encoded"
         return "separate"
 
@@ -391,6 +403,10 @@ class Trainer:
         if self.loss == SOFTMAX:  # the padding columns of every class block stay zero
             full = np.zeros((self.classes, self.ld_x))
             full[:, : self.d_x] = b0.reshape(self.classes, self.d_x)
+            b0 = full.ravel()
+        if self.models > 1:  # every model starts from the single-model run's beta_0; padding columns stay zero
+            full = np.zeros((self.models, self.ld_x))
+            full[:, : self.d_x] = b0
             b0 = full.ravel()
         self.beta.zero_()
         self.beta[:d] = torch.from_numpy(b0).to(self.beta.device)
@@ -621,6 +637,7 @@ class Trainer:
         cfg, env, sch = self.cfg, self.env, self.scheme
         R, W, K = cfg.num_itrs, cfg.n_workers, self.K
         eta = cfg.eta()
+        sweep_eta = cfg.sweep_etas()  # [M, R] in a sweep run
         col = ArrivalCollector(W, sch.group_of, sch.n_groups, env.gpu, cfg.tie_seed_value)
         col.set_shards(self.n_shards)
         col.set_skip_stale(self.skip_stale)
@@ -690,12 +707,17 @@ class Trainer:
                             self.tx.before_read(slot, self.rem_slot[key])
                         msgs.append(v)
                         coefs.append(c)
-                decay, gm, l2, theta, code = self.update.coeffs(i, float(eta[i]))
                 if env.gpu and not cfg.sync_update:
                     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     ev0.record(self.cs)
-                combine_update(msgs, coefs, self.beta, self.u, self.d, decay, gm, l2, theta, code,
-                               hist=self.hist[i], beta_w=self.beta_in[i + 1])
+                if self.models > 1:  # every model block with its own (alpha_k, lr_k)
+                    decay, gm, l2, theta, code = self.update.block_coeffs(i, sweep_eta[:, i], self.sweep_alpha)
+                    combine_update_blocks(msgs, coefs, self.beta, self.u, self.ld_x, self.d_x, decay, gm, l2, theta,
+                                          code, hist=self.hist[i], beta_w=self.beta_in[i + 1])
+                else:
+                    decay, gm, l2, theta, code = self.update.coeffs(i, float(eta[i]))
+                    combine_update(msgs, coefs, self.beta, self.u, self.d, decay, gm, l2, theta, code,
+                                   hist=self.hist[i], beta_w=self.beta_in[i + 1])
                 if env.gpu:
                     if cfg.sync_update:
                         self.upd_ev.record(self.cs)
@@ -762,6 +784,8 @@ class Trainer:
                                   "workers": sorted({int(m.worker) for m in self.local_msgs}),
                                   "messages": len(self.local_msgs),
                                   "partitions": len({p for m in self.local_msgs for p, _ in m.segments})}
+        if self.models > 1:
+            rep.update(models=self.models, sweep_alpha=list(self.sweep_alpha), sweep_lr=list(self.sweep_lr))
         rep.update({k: (round(float(v), 2) if isinstance(v, (int, float)) and not isinstance(v, bool) else v)
                     for k, v in self.rank_stats.items() if v is not None})
         kern = self._kernel_label()
@@ -834,6 +858,11 @@ class Trainer:
         pump.set_schedule([c[0] for c in co], [c[1] for c in co], [c[2] for c in co], [c[3] for c in co],
                           co[0][4] if co else 0, [float(x) for x in delay_table.ravel()], self.rule_kind,
                           self.rule_k, bool(self.drain))
+        if self.models > 1:  # per-model (decay, gm, l2), flat [R * M]; theta and the rule are common
+            se = cfg.sweep_etas()
+            bco = [self.update.block_coeffs(i, se[:, i], self.sweep_alpha) for i in range(R)]
+            pump.set_block_schedule(self.models, self.ld_x, self.d_x, [x for c in bco for x in c[0]],
+                                    [x for c in bco for x in c[1]], [x for c in bco for x in c[2]])
         if self.physical:  # remote messages are really late: the collector applies no virtual delay to them
             pump.set_remote_delays([float(x) for x in self._remote_delays(delay_table).ravel()])
         if self._clocks and tx is not None and (self.physical or cfg.device_records):
@@ -1210,6 +1239,12 @@ class Trainer:
         nxt = int(st["next_round"])
         if not 0 < nxt <= self.cfg.num_itrs:
             raise ValueError(f"checkpoint next_round {nxt} outside (0, {self.cfg.num_itrs}]")
+        if self.models > 1 or "sweep_alpha" in st:  # a sweep resumes only as the same sweep
+            want = (self.sweep_alpha, self.sweep_lr) if self.models > 1 else (None, None)
+            have = tuple(None if st.get(k) is None else [float(x) for x in st[k]] for k in ("sweep_alpha", "sweep_lr"))
+            if have != want:
+                raise ValueError(f"checkpoint {path} was written by a run with sweep lists alphas = {have[0]}, "
+                                 f"lrs = {have[1]}; this run has alphas = {want[0]}, lrs = {want[1]}")
         ld = self.ld
         if st["beta"].numel() != ld:
             raise ValueError("checkpoint beta has a different feature dimension")
@@ -1232,6 +1267,9 @@ class Trainer:
         state = {"next_round": next_round, "beta": self.beta.cpu(), "u": self.u.cpu(),
                  "hist": self.hist[:next_round].cpu(), "timeset": torch.from_numpy(timeset[:next_round].copy()),
                  "worker_timeset": torch.from_numpy(worker_timeset[:next_round].copy()), "scheme": self.key}
+        if self.models > 1:
+            state["sweep_alpha"] = [float(a) for a in self.sweep_alpha]
+            state["sweep_lr"] = [float(x) for x in self.sweep_lr]
         if getattr(self.scheme, "B", None) is not None:
             state["B"] = torch.from_numpy(np.ascontiguousarray(self.scheme.B, dtype=np.float64))
         tmp = path + ".tmp"

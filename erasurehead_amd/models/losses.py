@@ -25,6 +25,7 @@ B [C, d] and travels flattened class-major (on the device [C][ld_x], padding col
 """
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -139,6 +140,25 @@ def softmax_pack(B: np.ndarray, ld_x: int) -> np.ndarray:
     return out.ravel()
 
 
+def sweep_unpack(betaset: np.ndarray, models: int, d_x: int) -> np.ndarray:
+    """[R, M * ld_x] flattened model-major models of a sweep run (as the engine stores them) -> [R, M, d_x]."""
+    b = np.asarray(betaset)
+    b = b.reshape(1, -1) if b.ndim == 1 else b
+    if b.shape[1] % models or b.shape[1] // models < d_x:
+        raise ValueError(f"model length {b.shape[1]} is not {models} model blocks of >= {d_x} columns")
+    return b.reshape(b.shape[0], models, b.shape[1] // models)[:, :, :d_x]
+
+
+def sweep_pack(B: np.ndarray, ld_x: int) -> np.ndarray:
+    """[R, M, d_x] (or [M, d_x]) -> flattened model-major [R, M * ld_x] ([M * ld_x]) with zero padding columns."""
+    B = np.asarray(B, dtype=np.float64)
+    if B.shape[-1] > ld_x:
+        raise ValueError(f"{B.shape[-1]} columns do not fit blocks of {ld_x}")
+    out = np.zeros(B.shape[:-1] + (ld_x,))
+    out[..., : B.shape[-1]] = B
+    return out.reshape(B.shape[:-2] + (B.shape[-2] * ld_x,))
+
+
 _GRADS = {LOGISTIC: logistic_grad, LEAST_SQUARES: least_squares_grad, SQUARED_HINGE: squared_hinge_grad}
 
 
@@ -210,6 +230,12 @@ class UpdateRule:
         l2 = 2.0 * self.alpha * eta
         theta = 2.0 / (i + 2.0)
         return decay, gm, l2, theta, (0 if self.rule == "GD" else 1)
+
+    def block_coeffs(self, i: int, etas, alphas):
+        """Round i of a sweep run: ([decay_k], [gm_k], [l2_k], theta, rule_code) with model k's step etas[k] and L2
+        strength alphas[k] -- each exactly what coeffs() gives a single-model run with that alpha."""
+        co = [dataclasses.replace(self, alpha=float(a)).coeffs(i, float(e)) for e, a in zip(etas, alphas)]
+        return [c[0] for c in co], [c[1] for c in co], [c[2] for c in co], co[0][3], co[0][4]
 
     def apply(self, i: int, eta: float, beta: np.ndarray, u: np.ndarray, g: np.ndarray) -> None:
         """In-place host update (oracle of the combine_update kernel)."""

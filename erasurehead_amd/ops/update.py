@@ -24,6 +24,35 @@ def combine_update(msgs: Sequence[torch.Tensor], coefs: Sequence[float], beta: t
         C.combine_update(list(msgs), [float(c) for c in coefs], beta, u, hist, beta_w, g_out, int(d),
                          float(decay), float(gm), float(l2), float(theta), int(rule))
         return
+    _update_torch(msgs, coefs, beta, u, d, decay, gm, l2, theta, rule, hist, beta_w, g_out)
+
+
+def combine_update_blocks(msgs: Sequence[torch.Tensor], coefs: Sequence[float], beta: torch.Tensor, u: torch.Tensor,
+                          block_ld: int, d_x: int, decay: Sequence[float], gm: Sequence[float], l2: Sequence[float],
+                          theta: float, rule: int, hist: Optional[torch.Tensor] = None,
+                          beta_w: Optional[torch.Tensor] = None, g_out: Optional[torch.Tensor] = None) -> None:
+    """combine_update for a model of ``len(decay)`` blocks of ``block_ld`` columns (``d_x`` of them data) with their
+    own (decay, gm, l2): a multi-model run (ops/multimodel.py).  Block k gets exactly what ``combine_update`` gives
+    that block alone; padding columns stay zero."""
+    M = len(decay)
+    if not (len(gm) == M and len(l2) == M and beta.numel() == M * block_ld and 1 <= d_x <= block_ld):
+        raise ValueError(f"combine_update_blocks: {M} blocks of {block_ld} columns do not describe this model")
+    if beta.is_cuda:
+        C = native()
+        if len(msgs) > C.MAX_MSGS:
+            raise ValueError(f"at most {C.MAX_MSGS} messages per combine")
+        C.combine_update_blocks(list(msgs), [float(c) for c in coefs], beta, u, hist, beta_w, g_out, int(block_ld),
+                                int(d_x), [float(x) for x in decay], [float(x) for x in gm], [float(x) for x in l2],
+                                float(theta), int(rule))
+        return
+    for k in range(M):
+        s = slice(k * block_ld, (k + 1) * block_ld)
+        _update_torch([m[s] for m in msgs], coefs, beta[s], u[s], d_x, decay[k], gm[k], l2[k], theta, rule,
+                      None if hist is None else hist[s], None if beta_w is None else beta_w[s],
+                      None if g_out is None else g_out[s])
+
+
+def _update_torch(msgs, coefs, beta, u, d, decay, gm, l2, theta, rule, hist, beta_w, g_out) -> None:
     g = torch.zeros(d, dtype=torch.float64)
     for m, c in zip(msgs, coefs):
         g += float(c) * m[:d].double()

@@ -7,7 +7,8 @@
 * ``--only sweep``: d in {256, 1000, 2048, 4096} x n in {1e5, 1e6, 4e6} x fp64/fp32 against the
   device-copy ceiling, distinct-row and replica-bundle layouts; ``--loss a,b,...`` times each named
   loss on the same data in the same process, in the order given (repeat names to alternate);
-  ``softmax`` among them times the one-pass multi-class kernel for every ``--classes C,...``;
+  ``softmax`` among them times the one-pass multi-class kernel for every ``--classes C,...`` and
+  ``multimodel`` the one-pass M-model kernel of an (alpha, lr) sweep for every ``--models M,...``;
 * sparse one-hot gradients on covtype / kc_house / amazon-shaped data (the reference's real
   datasets, synthetic stand-ins of the same shape): the ELL path against the generic
   sorted-COO path.
@@ -134,7 +135,7 @@ def scale_cases(out):
 
 
 def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_000), precs=("fp64", "fp32"),
-                losses=("logistic",), classes=(2,)):
+                losses=("logistic",), classes=(2,), models=(2,), layouts_only=None):
     """Shape sweep of the dense gradient against the device-copy ceiling (round-2 verdict item 6).
 
     For every (precision, d, n): n rows in 8 partitions, two message layouts -- ``naive`` (one
@@ -144,14 +145,19 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
     kernel's distinct-X read rate over it.  Every loss of ``losses`` runs on the same tensors, one after
     the other (the kernels are branch-free in the data, so beta's scale does not enter the time).
     ``softmax`` runs SoftmaxGradPlan on the same X with labels randint(0, C), once per C of ``classes``
-    (rows of at most 1024 columns, fp64 / fp32).
+    (rows of at most 1024 columns, fp64 / fp32; other precisions are skipped with a note).  ``multimodel`` runs
+    MultiModelGradPlan (logistic) on the same X and labels, once per M of ``models``; ``ms_per_model`` is its time
+    over M, to hold against the one-model logistic rows.
     """
     import torch
 
     from erasurehead_amd.models.losses import LOSS_NAMES
     from erasurehead_amd.ops import DenseGradPlan, SoftmaxGradPlan, get_precision
+    from erasurehead_amd.ops.multimodel import MultiModelGradPlan
 
     layouts = {"naive": [[p] for p in range(8)], "agc": [[0, 1, 2]] * 3 + [[3, 4, 5]] * 3 + [[6, 7]] * 2}
+    if layouts_only:
+        layouts = {k: v for k, v in layouts.items() if k in layouts_only}
     for prec_name in precs:
         prec = get_precision(prec_name)
         for d in ds:
@@ -170,6 +176,26 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
                 beta = torch.randn(prec.ld(d), device="cuda", dtype=prec.acc) * 0.01
                 for lay, msgs in layouts.items():
                     for loss in losses:
+                        if loss == "multimodel":
+                            for M in models:
+                                plan = MultiModelGradPlan([[(p, 1.0) for p in m] for m in msgs], parts, prec,
+                                                          LOSS_NAMES["logistic"], M, d)
+                                bM = torch.randn(plan.ld, device="cuda", dtype=prec.acc) * 0.01
+                                G = plan.out_buffer()[0]
+                                ms = _time(lambda: plan.run(bM, G), reps=20)
+                                distinct = 8 * nbytes / 1e12  # TB
+                                r = {"kernel": "grad_models_sweep", "precision": prec_name, "d": d, "n": n,
+                                     "layout": lay, "loss": "logistic", "models": M, "tasks": plan.ntasks, "ms": ms,
+                                     "ms_per_model": ms / M, "distinct_TBps": distinct / ms * 1e3,
+                                     "copy_TBps": ceiling, "frac": distinct / ms * 1e3 / ceiling}
+                                out.append(r)
+                                print(json.dumps(r), flush=True)
+                                del plan, G
+                            continue
+                        if loss == "softmax" and prec_name not in ("fp64", "fp32"):
+                            print(json.dumps({"kernel": "grad_softmax_sweep", "precision": prec_name,
+                                              "skipped": "softmax runs in fp64 or fp32 only"}), flush=True)
+                            continue
                         if loss == "softmax":
                             for C in classes:
                                 sm = {p: (X, torch.randint(0, C, (rpp,), device="cuda").to(prec.acc))
@@ -338,8 +364,10 @@ def main():
     ap.add_argument("--precs", default="fp64,fp32", help="--only sweep: precisions (fp64, fp32, bf16, fp32x64)")
     ap.add_argument("--loss", default="logistic",
                     help="--only sweep: losses timed on the same data, in order (logistic, least_squares, squared_hinge, "
-                         "softmax)")
+                         "softmax, multimodel = the M-model logistic kernel of an (alpha, lr) sweep)")
     ap.add_argument("--classes", default="2", help="--only sweep --loss softmax: class counts, e.g. 2,4,7,8")
+    ap.add_argument("--models", default="2", help="--only sweep --loss multimodel: model counts, e.g. 2,4,8")
+    ap.add_argument("--sweep-layouts", default=None, help="--only sweep: naive,agc (default: both)")
     ap.add_argument("--sparse-shapes", default="covtype,kc_house_data,amazon-dataset", help="--only sparse: datasets")
     ap.add_argument("--ell-only", action="store_true", help="--only sparse: skip the CSR row pass")
     ap.add_argument("--sparse-layouts", default=None, help="--only sparse: naive,s1_replicas,frc_s1 (default: all)")
@@ -367,8 +395,8 @@ def main():
     from erasurehead_amd.models.losses import LOSS_CHOICES
 
     losses = tuple(a.loss.split(","))
-    if any(x not in LOSS_CHOICES for x in losses):
-        ap.error(f"--loss: names from {sorted(LOSS_CHOICES)}")
+    if any(x not in LOSS_CHOICES and x != "multimodel" for x in losses):
+        ap.error(f"--loss: names from {sorted(LOSS_CHOICES) + ['multimodel']}")
     out = []
     if a.only in (None, "dense"):
         dense_cases(out)
@@ -378,7 +406,9 @@ def main():
         eval_cases(out)
     if a.only == "sweep":
         sweep_cases(out, ds=tuple(int(x) for x in a.ds.split(",")), ns=tuple(int(float(x)) for x in a.ns.split(",")),
-                    precs=tuple(a.precs.split(",")), losses=losses, classes=tuple(int(c) for c in a.classes.split(",")))
+                    precs=tuple(a.precs.split(",")), losses=losses, classes=tuple(int(c) for c in a.classes.split(",")),
+                    models=tuple(int(m) for m in a.models.split(",")),
+                    layouts_only=a.sweep_layouts.split(",") if a.sweep_layouts else None)
     if a.only == "choices":
         if a.shapes:
             choice_cases(out, [(p, int(d), int(float(n))) for p, d, n in (x.split(":") for x in a.shapes.split(","))],
