@@ -250,6 +250,18 @@ struct BlockCoefs {
 hipError_t combine_update_blocks_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* u,
                                         double* hist, void* beta_w, double* g_out, const BlockCoefs& bc, double theta,
                                         int rule, hipStream_t st, long long* stamp = nullptr);
+// The same combine + update followed by the proximal step of an L1 penalty (lasso / elastic net): block k's new
+// beta is S_t(x) = |x| <= t ? +0.0 : x - copysign(t, x) of combine_update's new beta x with t = thr[k]
+// (NaN and +-inf pass through, -0.0 becomes +0.0), and the AGD momentum u is formed from the thresholded beta.
+// One kernel for a single model (nblocks = 1, block_ld = ld, d_x = d) and a multi-model run.  A negative or
+// NaN threshold returns hipErrorInvalidValue and launches nothing, as the shape errors of the blocks launch do.
+struct ProxCoefs {
+  int nblocks, block_ld, d_x;
+  double decay[kMaxBlocks], gm[kMaxBlocks], l2[kMaxBlocks], thr[kMaxBlocks];
+};
+hipError_t combine_update_prox_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* u,
+                                      double* hist, void* beta_w, double* g_out, const ProxCoefs& pc, double theta,
+                                      int rule, hipStream_t st, long long* stamp = nullptr);
 // one device timestamp (wall_clock64, hipDeviceAttributeWallClockRate kHz) into *out
 hipError_t stamp_launch(long long* out, hipStream_t st);
 

@@ -62,6 +62,84 @@ combine_update(const CombineArgs args, double* __restrict__ beta, double* __rest
   if (g_out) g_out[c] = g;
 }
 
+// Soft threshold, the proximal operator of t * |x|.  NaN fails the comparison and stays NaN, +-inf stays
+// +-inf, and every |x| <= t (-0.0 at t = 0 included) becomes +0.0.
+__device__ __forceinline__ double soft_threshold(double x, double t) {
+  return fabs(x) <= t ? 0.0 : x - copysign(t, x);
+}
+
+// combine_update_blocks followed by the proximal step of an L1 penalty (launchers.h ProxCoefs): the same
+// batched message loads, fma chain and update expressions, then beta' = S_thr(beta'), and the AGD momentum u
+// is formed from the thresholded beta'.  A single model is one block.  (It stands here, before
+// combine_update_blocks, so that the earlier instantiations keep their order at the end of the object's text.)
+template <typename M, typename W>
+__global__ void __launch_bounds__(256)
+combine_update_prox(const CombineArgs args, const ProxCoefs pc, double* __restrict__ beta, double* __restrict__ u,
+                    double* __restrict__ hist, W* __restrict__ beta_w, double* __restrict__ g_out, double theta,
+                    int rule, long long* __restrict__ stamp) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (stamp && c == 0) *stamp = wall_clock64();
+  if (c >= pc.nblocks * pc.block_ld) return;
+  const int blk = c / pc.block_ld;
+  if (c - blk * pc.block_ld >= pc.d_x) {  // padded columns of every block stay exactly zero
+    if (beta_w) beta_w[c] = W(0);
+    return;
+  }
+  double decay = pc.decay[0], gm = pc.gm[0], l2 = pc.l2[0], thr = pc.thr[0];
+#pragma unroll
+  for (int k = 1; k < kMaxBlocks; ++k)  // selects, not a dynamically indexed copy of the argument
+    if (k == blk) {
+      decay = pc.decay[k];
+      gm = pc.gm[k];
+      l2 = pc.l2[k];
+      thr = pc.thr[k];
+    }
+  double g = 0.0;
+  constexpr int kBatch = 8;
+  for (int m0 = 0; m0 < args.nmsg; m0 += kBatch) {
+    double v[kBatch];
+#pragma unroll
+    for (int k = 0; k < kBatch; ++k)
+      v[k] = m0 + k < args.nmsg ? static_cast<double>(static_cast<const M*>(args.msg[m0 + k])[c]) : 0.0;
+#pragma unroll
+    for (int k = 0; k < kBatch; ++k)
+      if (m0 + k < args.nmsg) g = fma(args.coef[m0 + k], v[k], g);
+  }
+  const double b = beta[c];
+  double nb;
+  if (rule == 0) {  // GD
+    nb = soft_threshold(decay * b - gm * g, thr);
+  } else {  // AGD
+    const double yt = (1.0 - theta) * b + theta * u[c];
+    nb = soft_threshold(yt - gm * g - l2 * b, thr);
+    u[c] = b + (nb - b) * (1.0 / theta);
+  }
+  beta[c] = nb;
+  if (hist) hist[c] = nb;
+  if (beta_w) beta_w[c] = static_cast<W>(nb);
+  if (g_out) g_out[c] = g;
+}
+
+hipError_t combine_update_prox_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* u,
+                                      double* hist, void* beta_w, double* g_out, const ProxCoefs& pc, double theta,
+                                      int rule, hipStream_t st, long long* stamp) {
+  if (pc.nblocks < 1 || pc.nblocks > kMaxBlocks || pc.block_ld < 1 || pc.d_x < 1 || pc.d_x > pc.block_ld ||
+      (msg_dtype != 0 && msg_dtype != 1) || (w_dtype != 0 && w_dtype != 1))
+    return hipErrorInvalidValue;
+  for (int k = 0; k < pc.nblocks; ++k)
+    if (!(pc.thr[k] >= 0.0)) return hipErrorInvalidValue;  // negative or NaN
+  const dim3 block(256), grid(ceil_div(pc.nblocks * pc.block_ld, 256));
+  if (msg_dtype == 0 && w_dtype == 0)
+    hipLaunchKernelGGL((combine_update_prox<double, double>), grid, block, 0, st, args, pc, beta, u, hist, (double*)beta_w, g_out, theta, rule, stamp);
+  else if (msg_dtype == 0 && w_dtype == 1)
+    hipLaunchKernelGGL((combine_update_prox<double, float>), grid, block, 0, st, args, pc, beta, u, hist, (float*)beta_w, g_out, theta, rule, stamp);
+  else if (msg_dtype == 1 && w_dtype == 0)
+    hipLaunchKernelGGL((combine_update_prox<float, double>), grid, block, 0, st, args, pc, beta, u, hist, (double*)beta_w, g_out, theta, rule, stamp);
+  else
+    hipLaunchKernelGGL((combine_update_prox<float, float>), grid, block, 0, st, args, pc, beta, u, hist, (float*)beta_w, g_out, theta, rule, stamp);
+  return hipGetLastError();
+}
+
 // combine_update for a model of several blocks with per-block coefficients (launchers.h BlockCoefs): the
 // same batched message loads, the same fma chain and the same update expressions, so block k is bitwise
 // what combine_update gives on that block alone with (decay_k, gm_k, l2_k).

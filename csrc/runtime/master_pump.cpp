@@ -270,6 +270,19 @@ class MasterPump {
     bl2_ = l2;
   }
 
+  // L1 / elastic net: round i ends with the soft threshold thr[i] (one model) or thr[i * M + k] (block k of a
+  // multi-model run; call after set_block_schedule).  From then on combine() launches combine_update_prox with the
+  // coefficients of set_schedule / set_block_schedule, and the rounds take neither fused update path (the device
+  // arbiter, the slab reduction's update), as a multi-model run takes neither.
+  void set_prox_schedule(const std::vector<double>& thr) {
+    arb_ready_ = false;
+    const size_t n = static_cast<size_t>(R_) * (blocks_ ? blocks_ : 1);
+    need(thr.size() == n, "prox schedule must be [R] or [R * models]");
+    for (double t : thr) need(t >= 0.0, "prox schedule: thresholds must be >= 0 (and not NaN)");
+    need(n > 0, "prox schedule: no rounds");
+    prox_ = thr;
+  }
+
   // --delay-on worker: virtual delays the collector applies to REMOTE messages (the worker ranks
   // are physically late themselves); default: the same table as the local messages.
   void set_remote_delays(const std::vector<double>& delays) {
@@ -542,7 +555,8 @@ class MasterPump {
         if (!graph) decode_round(i);
         char* g = ring_slot(G_, g_rows_, i);
         eh::LocalUpdate up;
-        if (fused_update_ && launcher_->can_fuse_update() && local_update(i, useds[i - a], g, st + i + 1, &up)) {
+        if (fused_update_ && prox_.empty() && launcher_->can_fuse_update() &&
+            local_update(i, useds[i - a], g, st + i + 1, &up)) {
           hcheck(launcher_->launch_update(beta_row(i), g, up, stream_), "local gradient + update");
           continue;
         }
@@ -597,6 +611,7 @@ class MasterPump {
 
   // Why rounds [a, b) cannot run on the device arbiter ("" = they can).
   std::string device_blocker(int a, int b) const {
+    if (!prox_.empty()) return "proximal step after the update (L1 penalty)";
     if (blocks_) return "per-model update coefficients (multi-model run)";
     if (comm_) return "messages travel over " + comm_->kind() + " (the arbiter polls IPC counters)";
     if (remote_.empty() || arb_src_.empty()) return "no remote workers";
@@ -831,7 +846,24 @@ class MasterPump {
       if (!ev.second) ev.second = make_event(hipEventDefault);
       record_timed(ev.first, stream_);
     }
-    if (blocks_) {
+    if (!prox_.empty()) {  // one block (d_ of ld_ columns) or the block schedule's, then the soft threshold
+      const int nb = blocks_ ? blocks_ : 1;
+      eh::ProxCoefs pc{};
+      pc.nblocks = nb;
+      pc.block_ld = blocks_ ? block_ld_ : ld_;
+      pc.d_x = blocks_ ? block_dx_ : d_;
+      for (int k = 0; k < nb; ++k) {
+        const size_t j = static_cast<size_t>(i) * nb + k;
+        pc.decay[k] = blocks_ ? bdecay_[j] : decay_[i];
+        pc.gm[k] = blocks_ ? bgm_[j] : gm_[i];
+        pc.l2[k] = blocks_ ? bl2_[j] : l2_[i];
+        pc.thr[k] = prox_[j];
+      }
+      hcheck(eh::combine_update_prox_launch(a, acc_, acc_, beta_.data_ptr<double>(), u_.data_ptr<double>(),
+                                            hist_.data_ptr<double>() + static_cast<int64_t>(i) * ld_, beta_row(i + 1),
+                                            nullptr, pc, theta_[i], update_rule_, stream_, stamp),
+             "combine_update_prox");
+    } else if (blocks_) {
       eh::BlockCoefs bc{};
       bc.nblocks = blocks_;
       bc.block_ld = block_ld_;
@@ -1133,6 +1165,7 @@ class MasterPump {
   std::vector<double> decay_, gm_, l2_, theta_, delays_, remote_delays_;
   int blocks_ = 0, block_ld_ = 0, block_dx_ = 0;  // set_block_schedule: per-model coefficients [R * blocks_]
   std::vector<double> bdecay_, bgm_, bl2_;
+  std::vector<double> prox_;  // set_prox_schedule: soft thresholds [R * max(1, blocks_)]; empty = no proximal step
   int repeat_ = 1;
   int update_rule_ = 0, stop_rule_ = 0, k_ = 0;
   bool drain_ = false;
@@ -1189,6 +1222,7 @@ void bind_master_pump(py::module& m) {
       .def("device_log", &MasterPump::device_log)
       .def("set_schedule", &MasterPump::set_schedule)
       .def("set_block_schedule", &MasterPump::set_block_schedule)
+      .def("set_prox_schedule", &MasterPump::set_prox_schedule)
       .def("set_decode", &MasterPump::set_decode)
       .def("add_table", &MasterPump::add_table)
       .def("begin", &MasterPump::begin, py::call_guard<py::gil_scoped_release>())

@@ -46,6 +46,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "round); zipped with --lrs, a single value is broadcast")
     g.add_argument("--lrs", type=parse_float_list, default=None, metavar="L1,L2,...",
                    help="sweep: one model per learning rate (zipped with --alphas; not with an explicit lr_schedule)")
+    g.add_argument("--l1", type=float, default=0.0,
+                   help="L1 strength: adds l1 * ||beta||_1 to the objective (lasso; elastic net with --alpha) through a "
+                        "soft threshold eta_i * l1 after every update")
+    g.add_argument("--l1s", type=parse_float_list, default=None, metavar="L1,L2,...",
+                   help="sweep: one model per L1 strength (a regularisation path in one run; zipped with --alphas / "
+                        "--lrs, a single value is broadcast)")
     g.add_argument("--seed", type=int, default=None)
     g.add_argument("--data", default="files", choices=["files", "synthetic"])
     g.add_argument("--data-seed", type=int, default=0)
@@ -137,7 +143,7 @@ def parse(argv: List[str]):
                     tie_break=a.tie_break, tie_seed=a.tie_seed, shard=a.shard,
                     integrity=not a.no_integrity, delay_on=a.delay_on, slow_ranks=parse_slow_ranks(a.slow_ranks),
                     dedicated_master=a.dedicated_master, device_records=a.device_records,
-                    sweep_alpha=a.alphas, sweep_lr=a.lrs)
+                    sweep_alpha=a.alphas, sweep_lr=a.lrs, l1=a.l1, sweep_l1=a.l1s)
     return cfg, a
 
 

@@ -53,6 +53,11 @@ class RunConfig:
     # The lists are zipped; an absent list or one of length 1 is broadcast (absent: the run's alpha / lr).
     sweep_alpha: Optional[List[float]] = None
     sweep_lr: Optional[List[float]] = None
+    # L1 strength (lambda) of the penalty l1 * ||beta||_1: a soft threshold eta_i * l1 after every update of the
+    # master (lasso / elastic net with alpha; models/losses.py UpdateRule).  sweep_l1: one lambda per model of a
+    # sweep, zipped with sweep_alpha / sweep_lr under the same rules; alone it makes a sweep of len(sweep_l1) models.
+    l1: float = 0.0
+    sweep_l1: Optional[List[float]] = None
     seed: Optional[int] = None  # beta_0 / B matrix seed (reference: unseeded)
     data: str = "files"  # files | synthetic (on-device generator, no files)
     data_seed: int = 0
@@ -132,19 +137,33 @@ class RunConfig:
             raise ValueError(f"classes is an option of the softmax loss, not of {self.loss!r}")
         if any(int(f) < 1 for f in self.slow_ranks.values()):
             raise ValueError("slow rank factors must be integers >= 1")
+        self.l1 = float(self.l1)
+        if not (np.isfinite(self.l1) and self.l1 >= 0):
+            raise ValueError(f"l1 must be a finite value >= 0, got {self.l1}")
         self.sweep()  # the sweep's limits, each a ValueError that names it
 
-    def sweep(self) -> Optional[List[Tuple[float, float]]]:
-        """The (alpha_k, lr_k) of every model of a sweep run, or None without --alphas / --lrs."""
-        if self.sweep_alpha is None and self.sweep_lr is None:
+    def _sweep_lists(self) -> Optional[Tuple[List[float], List[float], List[float]]]:
+        """([alpha_k], [lr_k], [l1_k]) of a sweep run, every list broadcast to the M models; None without a list."""
+        if self.sweep_alpha is None and self.sweep_lr is None and self.sweep_l1 is None:
             return None
         al = [float(a) for a in (self.sweep_alpha if self.sweep_alpha is not None else [self.alpha_value])]
         lr = [float(x) for x in (self.sweep_lr if self.sweep_lr is not None else [self.lr])]
+        l1 = [float(x) for x in (self.sweep_l1 if self.sweep_l1 is not None else [self.l1])]
         if not al or not lr:
             raise ValueError("sweep: --alphas / --lrs must not be empty")
+        if not l1:
+            raise ValueError("sweep: --l1s must not be empty")
+        if any(not (np.isfinite(x) and x >= 0) for x in l1):
+            raise ValueError(f"sweep: every value of --l1s must be finite and >= 0, got {l1}")
+        if self.sweep_l1 is not None and self.l1 != 0:
+            raise ValueError("sweep: --l1s gives every model's L1 strength; it cannot be combined with --l1")
         if len(al) > 1 and len(lr) > 1 and len(al) != len(lr):
             raise ValueError(f"sweep: {len(al)} alphas and {len(lr)} lrs: lists longer than 1 must have equal lengths")
-        M = max(len(al), len(lr))
+        longest = max(len(al), len(lr))
+        if len(l1) > 1 and longest > 1 and len(l1) != longest:
+            raise ValueError(f"sweep: {len(l1)} l1s against {longest} alphas / lrs: lists longer than 1 must have "
+                             f"equal lengths")
+        M = max(longest, len(l1))
         if not SWEEP_MIN_MODELS <= M <= SWEEP_MAX_MODELS:
             raise ValueError(f"sweep: {M} models; a sweep trains {SWEEP_MIN_MODELS}..{SWEEP_MAX_MODELS} models "
                              f"(give {SWEEP_MIN_MODELS} to {SWEEP_MAX_MODELS} values in --alphas or --lrs)")
@@ -155,14 +174,25 @@ class RunConfig:
                              "(logistic, least_squares, squared_hinge or auto)")
         al = al * M if len(al) == 1 else al
         lr = lr * M if len(lr) == 1 else lr
-        return list(zip(al, lr))
+        l1 = l1 * M if len(l1) == 1 else l1
+        return al, lr, l1
+
+    def sweep(self) -> Optional[List[Tuple[float, float]]]:
+        """The (alpha_k, lr_k) of every model of a sweep run, or None without --alphas / --lrs / --l1s."""
+        sw = self._sweep_lists()
+        return None if sw is None else list(zip(sw[0], sw[1]))
+
+    def sweep_l1s(self) -> Optional[List[float]]:
+        """The L1 strength of every model of a sweep run (--l1s, or --l1 broadcast), or None without a sweep."""
+        sw = self._sweep_lists()
+        return None if sw is None else list(sw[2])
 
     def sweep_etas(self) -> Optional[np.ndarray]:
         """[M, num_itrs]: model k's step schedule, eta() evaluated with lr = lr_k."""
         sw = self.sweep()
         if sw is None:
             return None
-        return np.stack([dataclasses.replace(self, lr=lr, sweep_alpha=None, sweep_lr=None).eta()[: self.num_itrs]
+        return np.stack([dataclasses.replace(self, lr=lr, sweep_alpha=None, sweep_lr=None, sweep_l1=None).eta()[: self.num_itrs]
                          for _, lr in sw])
 
     @property

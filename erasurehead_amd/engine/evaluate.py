@@ -13,6 +13,10 @@ result names carry the prefix ``sweep{k}_`` (before ``sqhinge_`` where that appl
 Softmax runs are scored by cross-entropy and accuracy: the console line carries the accuracy where the
 logistic line has the AUC, ``EvalResult.auc`` (and the ``auc`` result file) hold the accuracy, and the
 result names carry the prefix ``softmax_``.
+Runs with an L1 penalty (--l1 / --l1s, some lambda > 0) also report sparsity: ``EvalResult.nnz`` (the non-zero
+data columns of every iterate) and ``l1_penalty`` are filled for every run; with some lambda > 0 the console gets
+one line ``>> L1: l1 = ..., nnz = k of d`` per model, the ``>> Model k:`` line of a sweep names ``l1``, and an
+``nnz`` result file is written next to the ``auc`` file, under the same prefixes.
 """
 from __future__ import annotations
 
@@ -43,6 +47,36 @@ class EvalResult:
     n_test: int
     files: Optional[Dict[str, str]] = None  # sweep runs: {"sweep{k}_" + key: path} of every model
     best: Optional[int] = None  # sweep runs (arrays [R, M]): the model with the lowest final test loss
+    nnz: Optional[np.ndarray] = None  # non-zero data columns of every iterate: [R], sweep [R, M]; softmax: all C blocks
+    l1_penalty: Optional[np.ndarray] = None  # l1 * ||beta||_1 of every iterate, shaped like nnz
+
+
+def sparsity(trainer: Trainer, betaset: np.ndarray):
+    """(nnz, l1_penalty) of every iterate over the data columns: [R], or [R, M] for a sweep run (softmax counts
+    over its C class blocks: they are one model with one lambda)."""
+    B = np.asarray(betaset, dtype=np.float64)
+    R, M = B.shape[0], getattr(trainer, "models", 1)
+    if M > 1:
+        blocks = B.reshape(R, M, trainer.ld_x)[:, :, : trainer.d_x]
+        l1 = np.asarray(trainer.sweep_l1, dtype=np.float64)
+        return np.count_nonzero(blocks, axis=2), np.abs(blocks).sum(axis=2) * l1
+    if is_multiclass(trainer.loss):
+        B = B.reshape(R, trainer.classes, trainer.ld_x)[:, :, : trainer.d_x].reshape(R, -1)
+    else:
+        B = B[:, : trainer.d]
+    return np.count_nonzero(B, axis=1), np.abs(B).sum(axis=1) * float(trainer.cfg.l1)
+
+
+def _nnz_line(l1: float, nnz: int, d: int) -> str:
+    return ">> L1: l1 = %g, nnz = %d of %d" % (l1, nnz, d)
+
+
+def _write_nnz(files: Dict[str, str], nnz, key: str = "nnz") -> None:
+    """The nnz result file next to the auc file: the same directory and prefixes, ``auc`` -> ``nnz``."""
+    auc_key = key[: -len("nnz")] + "auc"
+    head, tail = files[auc_key].rsplit("auc", 1)
+    files[key] = head + "nnz" + tail
+    dio.save_vector(np.asarray(nnz, dtype=np.float64), files[key])
 
 
 def eval_partitions(trainer: Trainer):
@@ -104,18 +138,23 @@ def _evaluate_softmax(trainer: Trainer, res: TrainResult, log, write: bool) -> E
     training_loss = tr_sum / max(1, n_train)
     testing_loss = te_sum / max(1, n_test)
     acc = hits / max(1, n_test)
+    nnz, pen = sparsity(trainer, res.betaset)
     if cfg.verbose:
         for i in range(R):
             log(report.softmax_line(i, training_loss[i], testing_loss[i], acc[i], res.timeset[i]))
+        if trainer.prox and R:
+            log(_nnz_line(cfg.l1, nnz[-1], C * d_x))
     files = None
     if write:
         names = {k: SOFTMAX_PREFIX + v for k, v in trainer.scheme.output_names(cfg.fix_quirks).items()}
         data_dir = getattr(trainer.source, "data_dir", None) or cfg.input_dir
         files = report.write_results(dio.results_dir(data_dir), names, training_loss, testing_loss, acc,
                                      res.timeset, res.worker_timeset, cfg.full_precision_outputs)
+        if trainer.prox:
+            _write_nnz(files, nnz)
     if cfg.verbose:
         log(">>> Done")
-    return EvalResult(training_loss, testing_loss, acc, n_train, n_test, files)
+    return EvalResult(training_loss, testing_loss, acc, n_train, n_test, files, nnz=nnz, l1_penalty=pen)
 
 
 def sweep_prefix(k: int) -> str:
@@ -142,6 +181,7 @@ def _evaluate_sweep(trainer: Trainer, res: TrainResult, log, write: bool) -> Eva
     testing_loss = (np.asarray(tsum) / max(1, n_test)).reshape(R, M)
     classify = is_classification(kind)
     auc = (auc_columns(yt, P) if classify else np.zeros(R * M)).reshape(R, M)
+    nnz, pen = sparsity(trainer, res.betaset)
     files = None
     do_write = write and (classify or cfg.save_linear)
     if do_write:
@@ -149,12 +189,15 @@ def _evaluate_sweep(trainer: Trainer, res: TrainResult, log, write: bool) -> Eva
         data_dir = getattr(trainer.source, "data_dir", None) or cfg.input_dir
     for k in range(M):
         if cfg.verbose:
-            log(">> Model %d: alpha = %g, lr = %g" % (k, trainer.sweep_alpha[k], trainer.sweep_lr[k]))
+            log(">> Model %d: alpha = %g, lr = %g" % (k, trainer.sweep_alpha[k], trainer.sweep_lr[k])
+                + (", l1 = %g" % trainer.sweep_l1[k] if trainer.prox else ""))
             for i in range(R):
                 if classify:
                     log(report.logistic_line(i, training_loss[i, k], testing_loss[i, k], auc[i, k], res.timeset[i]))
                 else:
                     log(report.linear_line(i, training_loss[i, k], testing_loss[i, k], res.timeset[i]))
+            if trainer.prox and R:
+                log(_nnz_line(trainer.sweep_l1[k], nnz[-1, k], d_x))
         if do_write:
             names = trainer.scheme.output_names(cfg.fix_quirks)
             if kind == SQUARED_HINGE:
@@ -163,13 +206,15 @@ def _evaluate_sweep(trainer: Trainer, res: TrainResult, log, write: bool) -> Eva
             out = report.write_results(dio.results_dir(data_dir), names, training_loss[:, k], testing_loss[:, k],
                                        auc[:, k], res.timeset, res.worker_timeset, cfg.full_precision_outputs)
             files.update({sweep_prefix(k) + key: v for key, v in out.items()})
+            if trainer.prox:
+                _write_nnz(files, nnz[:, k], sweep_prefix(k) + "nnz")
     final = testing_loss[-1] if R else np.zeros(M)
     best = int(np.argmin(np.where(np.isfinite(final), final, np.inf)))
     if cfg.verbose:
         log(">> Best model: %d (alpha = %g, lr = %g, final test loss %g)"
             % (best, trainer.sweep_alpha[best], trainer.sweep_lr[best], final[best]))
         log(">>> Done")
-    return EvalResult(training_loss, testing_loss, auc, n_train, n_test, files, best)
+    return EvalResult(training_loss, testing_loss, auc, n_train, n_test, files, best, nnz=nnz, l1_penalty=pen)
 
 
 def evaluate(trainer: Trainer, res: TrainResult, log=None, write: bool = True) -> EvalResult:
@@ -200,12 +245,15 @@ def evaluate(trainer: Trainer, res: TrainResult, log=None, write: bool = True) -
     testing_loss = tsum / max(1, n_test)
     classify = is_classification(kind)
     auc = auc_columns(yt, P) if classify else np.zeros(R)
+    nnz, pen = sparsity(trainer, res.betaset)
     if cfg.verbose:
         for i in range(R):
             if classify:
                 log(report.logistic_line(i, training_loss[i], testing_loss[i], auc[i], res.timeset[i]))
             else:
                 log(report.linear_line(i, training_loss[i], testing_loss[i], res.timeset[i]))
+        if trainer.prox and R:
+            log(_nnz_line(cfg.l1, nnz[-1], d))
     files = None
     if write and (classify or cfg.save_linear):
         names = trainer.scheme.output_names(cfg.fix_quirks)
@@ -214,6 +262,8 @@ def evaluate(trainer: Trainer, res: TrainResult, log=None, write: bool = True) -
         data_dir = getattr(trainer.source, "data_dir", None) or cfg.input_dir
         files = report.write_results(dio.results_dir(data_dir), names, training_loss, testing_loss, auc,
                                      res.timeset, res.worker_timeset, cfg.full_precision_outputs)
+        if trainer.prox:
+            _write_nnz(files, nnz)
     if cfg.verbose:
         log(">>> Done")
-    return EvalResult(training_loss, testing_loss, auc, n_train, n_test, files)
+    return EvalResult(training_loss, testing_loss, auc, n_train, n_test, files, nnz=nnz, l1_penalty=pen)

@@ -56,7 +56,7 @@ from ..ops.grad import DenseGradPlan, SharedGradPlan, SparseGradPlan
 from ..ops.softmax import SoftmaxGradPlan
 from ..ops.multimodel import MultiModelGradPlan
 from ..ops.precision import get_precision
-from ..ops.update import combine_update, combine_update_blocks
+from ..ops.update import combine_update, combine_update_blocks, combine_update_prox
 from ..parallel.collector import ArrivalCollector
 from ..parallel.dist import DistEnv
 from ..parallel.placement import make_shards, place_spread, place_units
@@ -186,7 +186,11 @@ class Trainer:
         self.sweep_lr = [x for _, x in sweep] if sweep else None
         self.rule_kind, self.rule_k = scheme.rule()
         self.update = UpdateRule("AGD" if scheme.fixed_agd else cfg.update_rule, cfg.alpha_value, cfg.n_rows,
-                                 scheme.grad_scale())
+                                 scheme.grad_scale(), float(cfg.l1))
+        # L1 / elastic net: a soft threshold after the master's update (ops/update.py combine_update_prox), taken
+        # only when some lambda > 0 -- a run whose lambdas are all 0 runs exactly the code it ran without them
+        self.sweep_l1 = cfg.sweep_l1s()
+        self.prox = any(x > 0 for x in (self.sweep_l1 if sweep else [cfg.l1]))
         self.drain_mode = cfg.drain or ("all" if scheme.drain else "carry")
         self.drain = self.drain_mode == "all"
         self.skip_stale = self.drain_mode == "lazy"
@@ -710,7 +714,17 @@ class Trainer:
                 if env.gpu and not cfg.sync_update:
                     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     ev0.record(self.cs)
-                if self.models > 1:  # every model block with its own (alpha_k, lr_k)
+                if self.prox:  # the update, then the soft threshold eta_i * l1 (per model in a sweep)
+                    if self.models > 1:
+                        decay, gm, l2, theta, code = self.update.block_coeffs(i, sweep_eta[:, i], self.sweep_alpha)
+                        thr = self.update.block_thresholds(i, sweep_eta[:, i], self.sweep_l1)
+                    else:
+                        decay, gm, l2, theta, code = self.update.coeffs(i, float(eta[i]))
+                        decay, gm, l2, thr = [decay], [gm], [l2], [self.update.threshold(i, float(eta[i]))]
+                    combine_update_prox(msgs, coefs, self.beta, self.u, self.ld_x if self.models > 1 else self.ld,
+                                        self.d_x if self.models > 1 else self.d, decay, gm, l2, thr, theta, code,
+                                        hist=self.hist[i], beta_w=self.beta_in[i + 1])
+                elif self.models > 1:  # every model block with its own (alpha_k, lr_k)
                     decay, gm, l2, theta, code = self.update.block_coeffs(i, sweep_eta[:, i], self.sweep_alpha)
                     combine_update_blocks(msgs, coefs, self.beta, self.u, self.ld_x, self.d_x, decay, gm, l2, theta,
                                           code, hist=self.hist[i], beta_w=self.beta_in[i + 1])
@@ -786,6 +800,7 @@ class Trainer:
                                   "partitions": len({p for m in self.local_msgs for p, _ in m.segments})}
         if self.models > 1:
             rep.update(models=self.models, sweep_alpha=list(self.sweep_alpha), sweep_lr=list(self.sweep_lr))
+        rep.update(l1=list(self.sweep_l1) if self.models > 1 else float(self.cfg.l1), prox=bool(self.prox))
         rep.update({k: (round(float(v), 2) if isinstance(v, (int, float)) and not isinstance(v, bool) else v)
                     for k, v in self.rank_stats.items() if v is not None})
         kern = self._kernel_label()
@@ -863,6 +878,12 @@ class Trainer:
             bco = [self.update.block_coeffs(i, se[:, i], self.sweep_alpha) for i in range(R)]
             pump.set_block_schedule(self.models, self.ld_x, self.d_x, [x for c in bco for x in c[0]],
                                     [x for c in bco for x in c[1]], [x for c in bco for x in c[2]])
+        if self.prox:  # soft thresholds [R] or [R * M]; the rounds then stay off both fused update paths
+            if self.models > 1:
+                thr = [t for i in range(R) for t in self.update.block_thresholds(i, se[:, i], self.sweep_l1)]
+            else:
+                thr = [self.update.threshold(i, float(eta[i])) for i in range(R)]
+            pump.set_prox_schedule(thr)
         if self.physical:  # remote messages are really late: the collector applies no virtual delay to them
             pump.set_remote_delays([float(x) for x in self._remote_delays(delay_table).ravel()])
         if self._clocks and tx is not None and (self.physical or cfg.device_records):
@@ -1245,6 +1266,16 @@ class Trainer:
             if have != want:
                 raise ValueError(f"checkpoint {path} was written by a run with sweep lists alphas = {have[0]}, "
                                  f"lrs = {have[1]}; this run has alphas = {want[0]}, lrs = {want[1]}")
+        # the L1 strength likewise; a checkpoint without the key was written without an L1 penalty
+        have_l1 = float(st.get("l1", 0.0))
+        if have_l1 != float(self.cfg.l1):
+            raise ValueError(f"checkpoint {path} was written by a run with l1 = {have_l1:g}; this run has "
+                             f"l1 = {float(self.cfg.l1):g}")
+        if self.models > 1:
+            have_l1s = [float(x) for x in st["sweep_l1"]] if st.get("sweep_l1") is not None else [0.0] * self.models
+            if have_l1s != [float(x) for x in self.sweep_l1]:
+                raise ValueError(f"checkpoint {path} was written by a run with sweep_l1 = {have_l1s}; this run has "
+                                 f"sweep_l1 = {list(self.sweep_l1)}")
         ld = self.ld
         if st["beta"].numel() != ld:
             raise ValueError("checkpoint beta has a different feature dimension")
@@ -1270,6 +1301,8 @@ class Trainer:
         if self.models > 1:
             state["sweep_alpha"] = [float(a) for a in self.sweep_alpha]
             state["sweep_lr"] = [float(x) for x in self.sweep_lr]
+            state["sweep_l1"] = [float(x) for x in self.sweep_l1]
+        state["l1"] = float(self.cfg.l1)
         if getattr(self.scheme, "B", None) is not None:
             state["B"] = torch.from_numpy(np.ascontiguousarray(self.scheme.B, dtype=np.float64))
         tmp = path + ".tmp"

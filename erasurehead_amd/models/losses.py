@@ -214,14 +214,28 @@ def roc_auc(y: np.ndarray, scores: np.ndarray, pos_label: float = 1) -> float:
     return float(u / (n_pos * n_neg))
 
 
+def soft_threshold(x, t):
+    """S_t(x) = (|x| <= t) ? +0.0 : x - copysign(t, x), the proximal operator of t * |x| (t >= 0, scalar or
+    broadcastable).  NaN stays NaN, +-inf stays +-inf, and every |x| <= t (-0.0 at t = 0 included) becomes +0.0:
+    the oracle of the soft threshold in combine_update_prox (csrc/kernels/update.hip)."""
+    x = np.asarray(x, dtype=np.float64)
+    t = np.asarray(t, dtype=np.float64)
+    if np.any(~(t >= 0)):
+        raise ValueError("soft_threshold: the threshold must be >= 0")
+    with np.errstate(invalid="ignore"):
+        return np.where(np.abs(x) <= t, 0.0, x - np.copysign(t, x))
+
+
 @dataclass
 class UpdateRule:
-    """GD / AGD with the reference's constants (alpha = 1/n_rows, eta schedule)."""
+    """GD / AGD with the reference's constants (alpha = 1/n_rows, eta schedule), and optionally the proximal
+    step of an L1 penalty l1 * ||beta||_1 (lasso / elastic net) after every update."""
 
     rule: str  # "GD" | "AGD"
     alpha: float
     n_samples: int
     grad_scale: float = 1.0
+    l1: float = 0.0  # L1 strength (lambda); 0 = no proximal step
 
     def coeffs(self, i: int, eta: float) -> Tuple[float, float, float, float, int]:
         """(decay, grad_multiplier, l2, theta, rule_code) for round i."""
@@ -237,13 +251,28 @@ class UpdateRule:
         co = [dataclasses.replace(self, alpha=float(a)).coeffs(i, float(e)) for e, a in zip(etas, alphas)]
         return [c[0] for c in co], [c[1] for c in co], [c[2] for c in co], co[0][3], co[0][4]
 
+    def threshold(self, i: int, eta: float) -> float:
+        """Round i's soft threshold t_i = eta_i * l1.  grad_scale does not enter: it rescales the gradient
+        multiplier only (avoidstragg), and the penalty is not part of the gradient."""
+        return float(eta) * float(self.l1)
+
+    def block_thresholds(self, i: int, etas, l1s):
+        """Round i of a sweep run: [t_k] with model k's step etas[k] and L1 strength l1s[k]."""
+        return [dataclasses.replace(self, l1=float(l)).threshold(i, float(e)) for e, l in zip(etas, l1s)]
+
     def apply(self, i: int, eta: float, beta: np.ndarray, u: np.ndarray, g: np.ndarray) -> None:
-        """In-place host update (oracle of the combine_update kernel)."""
+        """In-place host update (oracle of the combine_update kernel; with l1 > 0 of combine_update_prox: the new
+        beta is soft-thresholded and the AGD momentum is formed from the thresholded beta)."""
         decay, gm, l2, theta, code = self.coeffs(i, eta)
+        prox = self.l1 > 0
         if code == 0:
             np.subtract(decay * beta, gm * g, out=beta)
+            if prox:
+                beta[:] = soft_threshold(beta, self.threshold(i, eta))
         else:
             ytemp = (1 - theta) * beta + theta * u
             betatemp = ytemp - gm * g - l2 * beta
+            if prox:
+                betatemp = soft_threshold(betatemp, self.threshold(i, eta))
             u[:] = beta + (betatemp - beta) * (1 / theta)
             beta[:] = betatemp

@@ -4,4 +4,4 @@ from .grad import DenseGradPlan, SparseGradPlan, choose_cpl
 from .softmax import SoftmaxGradPlan
 from .multimodel import MultiModelGradPlan
 from .precision import PRECISIONS, Precision, get_precision
-from .update import combine_update, combine_update_blocks
+from .update import combine_update, combine_update_blocks, combine_update_prox
