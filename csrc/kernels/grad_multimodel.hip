@@ -16,12 +16,11 @@
 // (one two-value reduce-scatter), evaluates the residual on the reduced value, broadcasts the two
 // residuals with readlane and feeds the gradient FMAs from the same registers.  No logits / residual
 // arrays in LDS and one barrier per stage.
-// Every wave writes its partial sums to its own slab row [task][sub][M][ld]; models_reduce adds a
+// Every wave writes its partial sums to its own slab row [task][sub][M][ld]; blocks_reduce (grad_blocks.h) adds a
 // partition's slab rows in a fixed order (no atomics: bitwise reproducible) and writes exact zeros into
 // the padding columns [d_x, ld) of every model block.
-#include <algorithm>
-
 #include "common.h"
+#include "grad_blocks.h"
 #include "grad_dense.h"
 #include "launchers.h"
 #include "lds_dma.h"
@@ -30,15 +29,7 @@ namespace eh {
 
 namespace {
 
-constexpr int kMmWaves = 4;
-
-// rows per LDS stage: about 32 KiB, at least one row per wave, at most 32 (the labels of a stage are one
-// 256-byte LDS-DMA piece)
-inline int models_stage_rows(int rowbytes) { return std::min(32, std::max(4, 32768 / rowbytes)); }
-inline size_t models_lds_bytes(int srows, int rowbytes) {
-  const size_t data = (static_cast<size_t>(srows) * rowbytes + 1023) / 1024 * 1024;
-  return 2 * (data + 256);  // the ring: data, then 256 B of labels, twice
-}
+constexpr int kMmWaves = kBlockSubs;
 
 }  // namespace
 
@@ -157,49 +148,10 @@ grad_models(const Segment* __restrict__ segs, const Task* __restrict__ tasks, co
   }
 }
 
-// Gb[p][e] = sum of partition p's slab rows (tasks in table order, waves in order) for element e of the
-// model-major [M][ld] vector; padding columns are exact zeros.  (softmax_reduce's twin.)
-template <typename A>
-__global__ void __launch_bounds__(256)
-models_reduce(const A* __restrict__ slab, const int* __restrict__ part_task_begin, A* __restrict__ Gb, int D,
-              int d_x, int ld, int wpg, const int* __restrict__ gate) {
-  const int p = blockIdx.y;
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= D || gate_closed(gate)) return;
-  A s = A(0);
-  if (e % ld < d_x) {
-    const long long r0 = static_cast<long long>(part_task_begin[p]) * wpg;
-    const long long r1 = static_cast<long long>(part_task_begin[p + 1]) * wpg;
-    const A* __restrict__ col = slab + e;
-    for (long long r = r0; r < r1; ++r) s += col[r * D];
-  }
-  Gb[static_cast<long long>(p) * D + e] = s;
-}
-
-template <typename T, typename A, int CPL, int LOSS>
-static hipError_t launch_models(int M, const void* segs, const void* tasks, int ntasks, const int* ptb, int nparts,
-                                const void* beta, void* slab, void* Gb, int d_x, int ld, hipStream_t st,
-                                const int* gate) {
-  const int rowbytes = ld * static_cast<int>(sizeof(T));
-  const int srows = models_stage_rows(rowbytes);
-  const size_t lds = models_lds_bytes(srows, rowbytes);
-  auto kern = grad_models<T, A, CPL, LOSS>;
-  if (const hipError_t e = allow_dynamic_lds(kern, lds); e != hipSuccess) return e;
-  if (ntasks > 0)
-    hipLaunchKernelGGL(kern, dim3(ntasks), dim3(64 * kMmWaves), lds, st, static_cast<const Segment*>(segs),
-                       static_cast<const Task*>(tasks), static_cast<const A*>(beta), static_cast<A*>(slab), M, ld, srows,
-                       gate);
-  const int D = M * ld;
-  const int wpg = kMmWaves / ((M + 1) / 2);
-  hipLaunchKernelGGL(models_reduce<A>, dim3(ceil_div(D, 256), nparts), dim3(256), 0, st, static_cast<const A*>(slab),
-                     ptb, static_cast<A*>(Gb), D, d_x, ld, wpg, gate);
-  return hipGetLastError();
-}
-
 hipError_t grad_models_launch(int dtype, int loss, int models, const void* segs, const void* tasks, int ntasks,
                               const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb, int d_x,
                               int ld_x, hipStream_t st, const int* gate) {
-  if (models < kModelsMin || models > kModelsMax || ld_x < 1 || ld_x > kModelsMaxLd || d_x < 1 || d_x > ld_x ||
+  if (models < kMinBlocks || models > kMaxBlocks || ld_x < 1 || ld_x > kBlockMaxLd || d_x < 1 || d_x > ld_x ||
       (dtype != 0 && dtype != 1 && dtype != 3) || ld_x % storage_vec(dtype) != 0 || loss < 0 || loss > kSquaredHinge)
     return hipErrorInvalidValue;
   if (nparts == 0) return hipSuccess;
@@ -211,12 +163,16 @@ hipError_t grad_models_launch(int dtype, int loss, int models, const void* segs,
     } else {
       return dispatch_loss(loss, [&](auto L) {
         constexpr int LOSS = decltype(L)::value;
-        return ld_x <= 256   ? launch_models<T, A, 4, LOSS>(models, segs, tasks, ntasks, part_task_begin, nparts, beta,
-                                                            slab, Gb, d_x, ld_x, st, gate)
-               : ld_x <= 512 ? launch_models<T, A, 8, LOSS>(models, segs, tasks, ntasks, part_task_begin, nparts, beta,
-                                                            slab, Gb, d_x, ld_x, st, gate)
-                             : launch_models<T, A, 16, LOSS>(models, segs, tasks, ntasks, part_task_begin, nparts, beta,
-                                                             slab, Gb, d_x, ld_x, st, gate);
+        const int rowbytes = ld_x * static_cast<int>(sizeof(T));
+        const int srows = blocks_stage_rows(rowbytes);
+        const size_t lds = blocks_ring_bytes(srows, rowbytes);
+        auto launch = [&](auto kern) {
+          return launch_blocks<A>(kern, lds, srows, models, segs, tasks, ntasks, part_task_begin, nparts, beta, slab,
+                                  Gb, d_x, ld_x, st, gate);
+        };
+        return ld_x <= 256   ? launch(grad_models<T, A, 4, LOSS>)
+               : ld_x <= 512 ? launch(grad_models<T, A, 8, LOSS>)
+                             : launch(grad_models<T, A, 16, LOSS>);
       });
     }
   });

@@ -21,12 +21,11 @@
 //   4. the wave re-reads each of its rows from LDS and accumulates r_c * x, the residuals read back as
 //      LDS broadcasts.
 // Labels are only ever compared with the class numbers, never used as an index.
-// Every wave writes its partial sums to its own slab row [task][sub][C][ld]; softmax_reduce adds a
+// Every wave writes its partial sums to its own slab row [task][sub][C][ld]; blocks_reduce (grad_blocks.h) adds a
 // partition's slab rows in a fixed order (no atomics: bitwise reproducible) and writes exact zeros
 // into the padding columns [d_x, ld) of every class block.
-#include <algorithm>
-
 #include "common.h"
+#include "grad_blocks.h"
 #include "grad_dense.h"
 #include "launchers.h"
 #include "lds_dma.h"
@@ -35,16 +34,8 @@ namespace eh {
 
 namespace {
 
-constexpr int kSmWaves = 4;
-constexpr int kSmZStride = 8;  // logits per row in LDS (kSoftmaxMaxClasses)
-
-// rows per LDS stage: about 32 KiB, at least one row per wave, at most 32 (the labels of a stage are one
-// 256-byte LDS-DMA piece)
-inline int softmax_stage_rows(int rowbytes) { return std::min(32, std::max(4, 32768 / rowbytes)); }
-inline size_t softmax_lds_bytes(int srows, int rowbytes, int acc_bytes) {
-  const size_t data = (static_cast<size_t>(srows) * rowbytes + 1023) / 1024 * 1024;
-  return 2 * (data + 256) + 2 * static_cast<size_t>(srows) * kSmZStride * acc_bytes;  // ring, logits, residuals
-}
+constexpr int kSmWaves = kBlockSubs;
+constexpr int kSmZStride = 8;  // logits per row in LDS (kMaxBlocks)
 
 }  // namespace
 
@@ -199,61 +190,32 @@ grad_softmax(const Segment* __restrict__ segs, const Task* __restrict__ tasks, c
   }
 }
 
-// Gb[p][e] = sum of partition p's slab rows (tasks in table order, waves in order) for element e of the
-// class-major [C][ld] vector; padding columns are exact zeros.
-template <typename A>
-__global__ void __launch_bounds__(256)
-softmax_reduce(const A* __restrict__ slab, const int* __restrict__ part_task_begin, A* __restrict__ Gb, int D,
-               int d_x, int ld, int wpg, const int* __restrict__ gate) {
-  const int p = blockIdx.y;
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= D || gate_closed(gate)) return;
-  A s = A(0);
-  if (e % ld < d_x) {
-    const long long r0 = static_cast<long long>(part_task_begin[p]) * wpg;
-    const long long r1 = static_cast<long long>(part_task_begin[p + 1]) * wpg;
-    const A* __restrict__ col = slab + e;
-    for (long long r = r0; r < r1; ++r) s += col[r * D];
-  }
-  Gb[static_cast<long long>(p) * D + e] = s;
-}
-
-template <typename T, typename A, int CPL>
-static hipError_t launch_softmax(int C, const void* segs, const void* tasks, int ntasks, const int* ptb, int nparts,
-                                 const void* beta, void* slab, void* Gb, int d_x, int ld, hipStream_t st,
-                                 const int* gate) {
-  const int rowbytes = ld * static_cast<int>(sizeof(T));
-  const int srows = softmax_stage_rows(rowbytes);
-  const size_t lds = softmax_lds_bytes(srows, rowbytes, sizeof(A));
-  auto kern = grad_softmax<T, A, CPL>;
-  if (const hipError_t e = allow_dynamic_lds(kern, lds); e != hipSuccess) return e;
-  if (ntasks > 0)
-    hipLaunchKernelGGL(kern, dim3(ntasks), dim3(64 * kSmWaves), lds, st, static_cast<const Segment*>(segs),
-                       static_cast<const Task*>(tasks), static_cast<const A*>(beta), static_cast<A*>(slab), C, ld, srows,
-                       gate);
-  const int D = C * ld;
-  const int wpg = kSmWaves / ((C + 1) / 2);
-  hipLaunchKernelGGL(softmax_reduce<A>, dim3(ceil_div(D, 256), nparts), dim3(256), 0, st, static_cast<const A*>(slab),
-                     ptb, static_cast<A*>(Gb), D, d_x, ld, wpg, gate);
-  return hipGetLastError();
-}
-
 hipError_t grad_softmax_launch(int dtype, int classes, const void* segs, const void* tasks, int ntasks,
                                const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb,
                                int d_x, int ld_x, hipStream_t st, const int* gate) {
-  if (classes < 2 || classes > kSoftmaxMaxClasses || ld_x < 1 || ld_x > kSoftmaxMaxLd || d_x < 1 || d_x > ld_x ||
-      (dtype != 0 && dtype != 1) || ld_x % (dtype == 0 ? 2 : 4) != 0)
+  if (classes < kMinBlocks || classes > kMaxBlocks || ld_x < 1 || ld_x > kBlockMaxLd || d_x < 1 || d_x > ld_x ||
+      (dtype != 0 && dtype != 1) || ld_x % storage_vec(dtype) != 0)
     return hipErrorInvalidValue;
   if (nparts == 0) return hipSuccess;
-#define EH_SM(T, A)                                                                                                 \
-  (ld_x <= 256   ? launch_softmax<T, A, 4>(classes, segs, tasks, ntasks, part_task_begin, nparts, beta, slab, Gb, d_x, \
-                                           ld_x, st, gate)                                                          \
-   : ld_x <= 512 ? launch_softmax<T, A, 8>(classes, segs, tasks, ntasks, part_task_begin, nparts, beta, slab, Gb, d_x, \
-                                           ld_x, st, gate)                                                          \
-                 : launch_softmax<T, A, 16>(classes, segs, tasks, ntasks, part_task_begin, nparts, beta, slab, Gb,   \
-                                            d_x, ld_x, st, gate))
-  return dtype == 0 ? EH_SM(double, double) : EH_SM(float, float);
-#undef EH_SM
+  return dispatch_storage(dtype, [&](auto S) {
+    using T = typename decltype(S)::T;
+    using A = typename decltype(S)::A;
+    if constexpr (!std::is_same_v<T, A>) {  // no bf16 or fp32x64 instance
+      return hipErrorInvalidValue;
+    } else {
+      const int rowbytes = ld_x * static_cast<int>(sizeof(T));
+      const int srows = blocks_stage_rows(rowbytes);
+      // behind the ring: the logits and the residuals of a stage, [srows][kSmZStride] each
+      const size_t lds = blocks_ring_bytes(srows, rowbytes, 2 * static_cast<size_t>(srows) * kSmZStride * sizeof(A));
+      auto launch = [&](auto kern) {
+        return launch_blocks<A>(kern, lds, srows, classes, segs, tasks, ntasks, part_task_begin, nparts, beta, slab, Gb,
+                                d_x, ld_x, st, gate);
+      };
+      return ld_x <= 256   ? launch(grad_softmax<T, A, 4>)
+             : ld_x <= 512 ? launch(grad_softmax<T, A, 8>)
+                           : launch(grad_softmax<T, A, 16>);
+    }
+  });
 }
 
 }  // namespace eh

@@ -152,33 +152,26 @@ constexpr int kSparseMaxDst = 4;
 hipError_t grad_sparse_launch(int dtype, int loss, const SparseArgs& a, const void* beta, hipStream_t st,
                               const int* gate = nullptr);
 
-// ---- multi-class softmax gradient (grad_softmax.hip) ----------------------------------------
-// Gb[p] = gradient of partition p's cross-entropy sum with coefficient 1, for every distinct local
-// partition in one pass over X: model beta and every Gb row are class-major [classes][ld_x] (D =
-// classes * ld_x elements), labels are class indices held as floats.  dtype 0 fp64 / 1 fp32,
-// 2 <= classes <= 8, ld_x <= 1024.  segs / tasks: the dense task table (grad_dense.h Segment / Task;
-// Task::slot = partition row of Gb, Task::slab = the task's index), tasks of one partition contiguous
-// and part_task_begin [nparts + 1] their ranges.  slab: [ntasks][kSoftmaxSubs][D] per-wave partial
-// sums (acc dtype), summed in a fixed order by the launch's second kernel; padding columns
-// [d_x, ld_x) of every class block of Gb are written as exact zeros.
-constexpr int kSoftmaxSubs = 4;
-constexpr int kSoftmaxMaxClasses = 8;
-constexpr int kSoftmaxMaxLd = 1024;
+// ---- blocked models: multi-class softmax and several scalar-loss models (grad_softmax.hip, grad_multimodel.hip) ----
+// One contract for both (grad_blocks.h).  The model beta and every Gb row are [blocks][ld_x] (D = blocks * ld_x
+// elements), Gb[p] = gradient of partition p's loss sum with coefficient 1, for every distinct local partition in
+// one pass over X.  segs / tasks: the dense task table (grad_dense.h Segment / Task; Task::slot = partition row of
+// Gb, Task::slab = the task's index), tasks of one partition contiguous and part_task_begin [nparts + 1] their
+// ranges.  slab: [ntasks][kBlockSubs][D] per-wave partial sums (acc dtype), summed in a fixed order by the launch's
+// second kernel (blocks_reduce); padding columns [d_x, ld_x) of every block of Gb are written as exact zeros.
+// kMinBlocks <= blocks <= kMaxBlocks, ld_x <= kBlockMaxLd and a multiple of the storage type's 16-byte vector;
+// anything else returns hipErrorInvalidValue and launches nothing.
+constexpr int kMinBlocks = 2;
+constexpr int kMaxBlocks = 8;      // also the blocks of one combine + update (BlockCoefs below)
+constexpr int kBlockSubs = 4;      // slab rows per task: the waves of a workgroup
+constexpr int kBlockMaxLd = 1024;  // 16 columns per lane
+// Softmax: blocks are classes, labels are class indices held as floats; dtype 0 fp64 / 1 fp32.
 hipError_t grad_softmax_launch(int dtype, int classes, const void* segs, const void* tasks, int ntasks,
                                const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb,
                                int d_x, int ld_x, hipStream_t st, const int* gate = nullptr);
-
-// ---- several scalar-loss models in one pass (grad_multimodel.hip) ------------------------------
-// The softmax launch's contract for M independent models of one scalar loss (an (alpha, lr) sweep): beta
-// and every Gb row are model-major [models][ld_x], Gb[p] block k = gradient of partition p's loss sum at
-// beta block k with coefficient 1.  dtype 0 fp64 / 1 fp32 / 3 fp32 storage with fp64 accumulators (beta,
-// labels, slab and Gb in the accumulator type), loss 0..2, 2 <= models <= 8, ld_x <= 1024 and a multiple
-// of the storage type's 16-byte vector; anything else returns hipErrorInvalidValue and launches nothing.
-// segs / tasks / part_task_begin / slab [ntasks][kModelsSubs][models * ld_x] as for grad_softmax_launch.
-constexpr int kModelsSubs = 4;
-constexpr int kModelsMin = 2;
-constexpr int kModelsMax = 8;
-constexpr int kModelsMaxLd = 1024;
+// M independent models of one scalar loss (an (alpha, lr) sweep): Gb[p] block k = gradient at beta block k.  dtype
+// 0 fp64 / 1 fp32 / 3 fp32 storage with fp64 accumulators (beta, labels, slab and Gb in the accumulator type),
+// loss 0..2.
 hipError_t grad_models_launch(int dtype, int loss, int models, const void* segs, const void* tasks, int ntasks,
                               const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb, int d_x,
                               int ld_x, hipStream_t st, const int* gate = nullptr);
@@ -239,14 +232,25 @@ hipError_t combine_update_launch(const CombineArgs& args, int msg_dtype, int w_d
                                  double l2, double theta, int rule, hipStream_t st,
                                  long long* stamp = nullptr);
 // The same combine + update for a model of several blocks with their own coefficients (a multi-model run,
-// grad_multimodel.hip): the vector is [nblocks][block_ld], column c takes decay / gm / l2 of block
+// grad_multimodel.hip; 1..kMaxBlocks of them): the vector is [nblocks][block_ld], column c takes decay / gm / l2 of block
 // c / block_ld and is padding when c % block_ld >= d_x (beta stays exactly zero there, beta_w gets zero);
 // theta and the rule are common.  Block k's output is bitwise combine_update's on that block alone.
-constexpr int kMaxBlocks = 8;
 struct BlockCoefs {
   int nblocks, block_ld, d_x;
   double decay[kMaxBlocks], gm[kMaxBlocks], l2[kMaxBlocks];
 };
+// nblocks <= kMaxBlocks blocks with (decay, gm, l2)[k] for block k; a ProxCoefs (below) takes its thr besides.
+inline void set_block_coefs(BlockCoefs& bc, int nblocks, int block_ld, int d_x, const double* decay, const double* gm,
+                            const double* l2) {
+  bc.nblocks = nblocks;
+  bc.block_ld = block_ld;
+  bc.d_x = d_x;
+  for (int k = 0; k < nblocks; ++k) {
+    bc.decay[k] = decay[k];
+    bc.gm[k] = gm[k];
+    bc.l2[k] = l2[k];
+  }
+}
 hipError_t combine_update_blocks_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* u,
                                         double* hist, void* beta_w, double* g_out, const BlockCoefs& bc, double theta,
                                         int rule, hipStream_t st, long long* stamp = nullptr);
@@ -255,10 +259,13 @@ hipError_t combine_update_blocks_launch(const CombineArgs& args, int msg_dtype, 
 // (NaN and +-inf pass through, -0.0 becomes +0.0), and the AGD momentum u is formed from the thresholded beta.
 // One kernel for a single model (nblocks = 1, block_ld = ld, d_x = d) and a multi-model run.  A negative or
 // NaN threshold returns hipErrorInvalidValue and launches nothing, as the shape errors of the blocks launch do.
-struct ProxCoefs {
-  int nblocks, block_ld, d_x;
-  double decay[kMaxBlocks], gm[kMaxBlocks], l2[kMaxBlocks], thr[kMaxBlocks];
+// BlockCoefs followed by the thresholds: nblocks, block_ld, d_x, decay, gm, l2, thr.  BlockCoefs ends on an 8-byte
+// boundary without tail padding, so the base sits at offset 0 and thr right behind it (asserted below).
+struct ProxCoefs : BlockCoefs {
+  double thr[kMaxBlocks];
 };
+static_assert(sizeof(BlockCoefs) == 16 + 3 * 8 * kMaxBlocks && sizeof(ProxCoefs) == sizeof(BlockCoefs) + 8 * kMaxBlocks,
+              "ProxCoefs is BlockCoefs' fields followed by thr[kMaxBlocks]");
 hipError_t combine_update_prox_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* u,
                                       double* hist, void* beta_w, double* g_out, const ProxCoefs& pc, double theta,
                                       int rule, hipStream_t st, long long* stamp = nullptr);

@@ -67,81 +67,43 @@ std::shared_ptr<GradLauncher> make_dense(int64_t dtype, int64_t loss, int64_t cp
   return g;
 }
 
-// Softmax plan (ops/softmax.py SoftmaxGradPlan): every distinct local partition once with coefficient 1
-// into rows of classes * ld_x elements; the plan's device encoding (set_encode) forms the messages unless
-// they are exactly the partitions.
-std::shared_ptr<GradLauncher> make_softmax(int64_t dtype, int64_t classes, const Tensor& segs, const Tensor& tasks,
+// Blocked-model plans (ops/blockplan.py BlockGradPlan): every distinct local partition once with coefficient 1 into
+// rows of blocks * ld_x elements; the plan's device encoding (set_encode) forms the messages unless they are exactly
+// the partitions.  kind 3: softmax, blocks = classes (ops/softmax.py); kind 4: `blocks` independent models of the
+// scalar loss `loss` (ops/multimodel.py).  who / what: the prefix and the block noun of the error texts.
+std::shared_ptr<GradLauncher> make_blocked(int kind, const std::string& who, const std::string& what, int64_t dtype,
+                                           int64_t loss, int64_t blocks, const Tensor& segs, const Tensor& tasks,
                                            const Tensor& slab, const Tensor& part_task_begin, int64_t d_x,
                                            int64_t ld_x) {
-  for (auto* t : {&segs, &tasks, &slab, &part_task_begin}) need_gpu(*t, "softmax plan operand");
-  need(dtype == 0 || dtype == 1, "softmax: fp64 or fp32 storage");
-  need(classes >= 2 && classes <= eh::kSoftmaxMaxClasses, "softmax: classes must be in 2..8");
-  need(ld_x >= 1 && ld_x <= eh::kSoftmaxMaxLd && d_x >= 1 && d_x <= ld_x && ld_x % (dtype == 0 ? 2 : 4) == 0,
-       "softmax: rows of at most 1024 columns, padded to the 16-byte vector width");
+  for (auto* t : {&segs, &tasks, &slab, &part_task_begin}) need_gpu(*t, (who + " plan operand").c_str());
+  need(blocks >= eh::kMinBlocks && blocks <= eh::kMaxBlocks, who + ": " + what + " must be in 2..8");
+  need(ld_x >= 1 && ld_x <= eh::kBlockMaxLd && d_x >= 1 && d_x <= ld_x && ld_x % eh::storage_vec((int)dtype) == 0,
+       who + ": rows of at most 1024 columns, padded to the 16-byte vector width");
   need(tasks.dim() == 2 && tasks.size(1) == 5 && tasks.scalar_type() == at::kInt, "tasks must be int32 [n,5]");
   need(segs.scalar_type() == at::kByte && segs.numel() % 32 == 0, "segs must be packed uint8 [nseg*32]");
   need(part_task_begin.scalar_type() == at::kInt && part_task_begin.numel() >= 1, "part_task_begin must be int32");
   auto g = std::make_shared<GradLauncher>();
-  g->kind = 3;
-  g->dtype = (int)dtype;
-  g->acc = (int)dtype;
-  g->loss = 3;
-  g->classes = (int)classes;
-  g->d_x = (int)d_x;
-  g->ld_x = (int)ld_x;
-  g->ld = (int)(classes * ld_x);
-  g->ntasks = (int)tasks.size(0);
-  g->nparts = (int)part_task_begin.numel() - 1;
-  g->nslots = g->rows = g->nparts;
-  need(acc_code(slab) == g->acc &&
-           slab.numel() >= (int64_t)std::max(1, g->ntasks) * eh::kSoftmaxSubs * g->ld,
-       "slab must hold [ntasks][4][classes * ld_x] partial sums (acc dtype)");
-  g->segs = segs.data_ptr();
-  g->tasks = tasks.data_ptr();
-  g->slab = slab.data_ptr();
-  g->stb = part_task_begin.data_ptr<int>();
-  g->keep = {segs, tasks, slab, part_task_begin};
-  return g;
-}
-
-// Multi-model plan (ops/multimodel.py MultiModelGradPlan): softmax's layout for `models` independent models of
-// one scalar loss; rows of models * ld_x elements, the device encoding forms the messages unless they are
-// exactly the partitions.
-std::shared_ptr<GradLauncher> make_multimodel(int64_t dtype, int64_t loss, int64_t models, const Tensor& segs,
-                                              const Tensor& tasks, const Tensor& slab, const Tensor& part_task_begin,
-                                              int64_t d_x, int64_t ld_x) {
-  for (auto* t : {&segs, &tasks, &slab, &part_task_begin}) need_gpu(*t, "multi-model plan operand");
-  need(dtype == 0 || dtype == 1 || dtype == 3, "multi-model: fp64, fp32 or fp32x64 (fp32 storage, fp64 accumulators)");
-  need(loss >= 0 && loss <= 2, "multi-model: logistic, least squares or squared hinge");
-  need(models >= eh::kModelsMin && models <= eh::kModelsMax, "multi-model: models must be in 2..8");
-  need(ld_x >= 1 && ld_x <= eh::kModelsMaxLd && d_x >= 1 && d_x <= ld_x && ld_x % eh::storage_vec((int)dtype) == 0,
-       "multi-model: rows of at most 1024 columns, padded to the 16-byte vector width");
-  need(tasks.dim() == 2 && tasks.size(1) == 5 && tasks.scalar_type() == at::kInt, "tasks must be int32 [n,5]");
-  need(segs.scalar_type() == at::kByte && segs.numel() % 32 == 0, "segs must be packed uint8 [nseg*32]");
-  need(part_task_begin.scalar_type() == at::kInt && part_task_begin.numel() >= 1, "part_task_begin must be int32");
-  auto g = std::make_shared<GradLauncher>();
-  g->kind = 4;
+  g->kind = kind;
   g->dtype = (int)dtype;
   g->acc = eh::storage_acc_code((int)dtype);
   g->loss = (int)loss;
-  g->classes = (int)models;
+  g->blocks = (int)blocks;
   g->d_x = (int)d_x;
   g->ld_x = (int)ld_x;
-  g->ld = (int)(models * ld_x);
+  g->ld = (int)(blocks * ld_x);
   g->ntasks = (int)tasks.size(0);
   g->nparts = (int)part_task_begin.numel() - 1;
   g->nslots = g->rows = g->nparts;
-  need(acc_code(slab) == g->acc &&
-           slab.numel() >= (int64_t)std::max(1, g->ntasks) * eh::kModelsSubs * g->ld,
-       "slab must hold [ntasks][4][models * ld_x] partial sums (acc dtype)");
+  need(acc_code(slab) == g->acc && slab.numel() >= (int64_t)std::max(1, g->ntasks) * eh::kBlockSubs * g->ld,
+       "slab must hold [ntasks][4][" + what + " * ld_x] partial sums (acc dtype)");
   {  // the kernel indexes segments, rows and slab rows with the task table: checked once, on the host
     const Tensor tc = tasks.cpu().contiguous(), pc = part_task_begin.cpu().contiguous(), sc = segs.cpu().contiguous();
-    const int* T = tc.data_ptr<int>();
+    const auto* T = reinterpret_cast<const eh::Task*>(tc.data_ptr<int>());
     const int* P = pc.data_ptr<int>();
     const auto* S = reinterpret_cast<const eh::Segment*>(sc.data_ptr<uint8_t>());
     const int64_t nseg = segs.numel() / 32;
     for (int k = 0; k < g->ntasks; ++k) {
-      const eh::Task& t = reinterpret_cast<const eh::Task*>(T)[k];
+      const eh::Task& t = T[k];
       need(t.seg >= 0 && t.seg < nseg && t.row_begin >= 0 && t.row_begin <= t.row_end &&
                t.row_end <= S[t.seg].nrows && t.slab >= 0 && t.slab < std::max(1, g->ntasks),
            "tasks: (slot, segment, row_begin <= row_end <= the segment's rows, slab row) inside the tables");
@@ -155,6 +117,21 @@ std::shared_ptr<GradLauncher> make_multimodel(int64_t dtype, int64_t loss, int64
   g->stb = part_task_begin.data_ptr<int>();
   g->keep = {segs, tasks, slab, part_task_begin};
   return g;
+}
+
+std::shared_ptr<GradLauncher> make_softmax(int64_t dtype, int64_t classes, const Tensor& segs, const Tensor& tasks,
+                                           const Tensor& slab, const Tensor& part_task_begin, int64_t d_x,
+                                           int64_t ld_x) {
+  need(dtype == 0 || dtype == 1, "softmax: fp64 or fp32 storage");
+  return make_blocked(3, "softmax", "classes", dtype, 3, classes, segs, tasks, slab, part_task_begin, d_x, ld_x);
+}
+
+std::shared_ptr<GradLauncher> make_multimodel(int64_t dtype, int64_t loss, int64_t models, const Tensor& segs,
+                                              const Tensor& tasks, const Tensor& slab, const Tensor& part_task_begin,
+                                              int64_t d_x, int64_t ld_x) {
+  need(dtype == 0 || dtype == 1 || dtype == 3, "multi-model: fp64, fp32 or fp32x64 (fp32 storage, fp64 accumulators)");
+  need(loss >= 0 && loss <= 2, "multi-model: logistic, least squares or squared hinge");
+  return make_blocked(4, "multi-model", "models", dtype, loss, models, segs, tasks, slab, part_task_begin, d_x, ld_x);
 }
 
 // Sparse plan (ops/grad.py SparseGradPlan): every distinct local partition once; the plan's device

@@ -1,6 +1,6 @@
 // GradLauncher: the per-round gradient launch of one rank's local messages, captured once from the
-// Python plan (ops/grad.py, ops/softmax.py) by the one validator of its kind (grad_launcher.cpp
-// make_dense / make_softmax / make_multimodel / make_sparse).  The plan object keeps every referenced tensor alive; the
+// Python plan (ops/grad.py, ops/blockplan.py) by the one validator of its kind (grad_launcher.cpp
+// make_dense / make_blocked / make_sparse).  The plan object keeps every referenced tensor alive; the
 // launcher also holds references.  The launch functions are inline: the pumps call them every round.
 #pragma once
 
@@ -28,10 +28,10 @@ struct GradLauncher {
   int acc = 0;
   int rows = 0;   // rows of G a launch writes: nslots, enc_slots after set_encode, the shared message rows (sparse dst)
   SparseArgs sa{};  // kind 2 (grad_sparse.hip); Gb is the launch's output
-  // kind 3 (grad_softmax.hip): classes, data columns / row stride (ld is the flattened classes * ld_x),
-  // distinct partitions (the rows the kernel writes) and their task ranges stb [nparts + 1]
-  // kind 4 (grad_multimodel.hip): the same layout with `classes` models of the scalar loss `loss`
-  int classes = 0, d_x = 0, ld_x = 0, nparts = 0;
+  // kind 3 / 4 (grad_softmax.hip: blocks are classes; grad_multimodel.hip: models of the scalar loss `loss`):
+  // blocks, data columns / row stride of a block (ld is the flattened blocks * ld_x), distinct partitions (the
+  // rows the kernel writes) and their task ranges stb [nparts + 1]
+  int blocks = 0, d_x = 0, ld_x = 0, nparts = 0;
   // optional device encoding (csrc/kernels/encode.hip): the kernels above write the distinct
   // partitions' gradients into Gb, then G[slot] = sum_k coef * Gb[idx] for the enc_slots messages
   void* Gb = nullptr;
@@ -101,10 +101,10 @@ struct GradLauncher {
         return grad_sparse_launch(acc, loss, a, beta, st, gate);
       }
       case 3:
-        return grad_softmax_launch(dtype, classes, segs, tasks, ntasks, stb, nparts, beta, slab, G, d_x, ld_x, st,
+        return grad_softmax_launch(dtype, blocks, segs, tasks, ntasks, stb, nparts, beta, slab, G, d_x, ld_x, st,
                                    gate);
       case 4:
-        return grad_models_launch(dtype, loss, classes, segs, tasks, ntasks, stb, nparts, beta, slab, G, d_x, ld_x, st,
+        return grad_models_launch(dtype, loss, blocks, segs, tasks, ntasks, stb, nparts, beta, slab, G, d_x, ld_x, st,
                                   gate);
       default:
         return hipErrorInvalidValue;

@@ -846,34 +846,25 @@ class MasterPump {
       if (!ev.second) ev.second = make_event(hipEventDefault);
       record_timed(ev.first, stream_);
     }
-    if (!prox_.empty()) {  // one block (d_ of ld_ columns) or the block schedule's, then the soft threshold
-      const int nb = blocks_ ? blocks_ : 1;
+    const int nb = blocks_ ? blocks_ : 1;
+    const size_t j = static_cast<size_t>(i) * nb;  // round i's coefficients in the per-block schedules
+    auto fill = [&](eh::BlockCoefs& bc) {  // the block schedule's, or one block (d_ of ld_ columns)
+      if (blocks_)
+        eh::set_block_coefs(bc, nb, block_ld_, block_dx_, &bdecay_[j], &bgm_[j], &bl2_[j]);
+      else
+        eh::set_block_coefs(bc, 1, ld_, d_, &decay_[i], &gm_[i], &l2_[i]);
+    };
+    if (!prox_.empty()) {  // then the soft threshold
       eh::ProxCoefs pc{};
-      pc.nblocks = nb;
-      pc.block_ld = blocks_ ? block_ld_ : ld_;
-      pc.d_x = blocks_ ? block_dx_ : d_;
-      for (int k = 0; k < nb; ++k) {
-        const size_t j = static_cast<size_t>(i) * nb + k;
-        pc.decay[k] = blocks_ ? bdecay_[j] : decay_[i];
-        pc.gm[k] = blocks_ ? bgm_[j] : gm_[i];
-        pc.l2[k] = blocks_ ? bl2_[j] : l2_[i];
-        pc.thr[k] = prox_[j];
-      }
+      fill(pc);
+      std::copy_n(&prox_[j], nb, pc.thr);
       hcheck(eh::combine_update_prox_launch(a, acc_, acc_, beta_.data_ptr<double>(), u_.data_ptr<double>(),
                                             hist_.data_ptr<double>() + static_cast<int64_t>(i) * ld_, beta_row(i + 1),
                                             nullptr, pc, theta_[i], update_rule_, stream_, stamp),
              "combine_update_prox");
     } else if (blocks_) {
       eh::BlockCoefs bc{};
-      bc.nblocks = blocks_;
-      bc.block_ld = block_ld_;
-      bc.d_x = block_dx_;
-      for (int k = 0; k < blocks_; ++k) {
-        const size_t j = static_cast<size_t>(i) * blocks_ + k;
-        bc.decay[k] = bdecay_[j];
-        bc.gm[k] = bgm_[j];
-        bc.l2[k] = bl2_[j];
-      }
+      fill(bc);
       hcheck(eh::combine_update_blocks_launch(a, acc_, acc_, beta_.data_ptr<double>(), u_.data_ptr<double>(),
                                               hist_.data_ptr<double>() + static_cast<int64_t>(i) * ld_, beta_row(i + 1),
                                               nullptr, bc, theta_[i], update_rule_, stream_, stamp),

@@ -38,7 +38,7 @@ SOFTMAX = 3
 LOSS_NAMES = {"logistic": LOGISTIC, "least_squares": LEAST_SQUARES, "squared_hinge": SQUARED_HINGE}
 # every loss a run can name (--loss): the per-row scalar losses above plus the multi-class model
 LOSS_CHOICES = {**LOSS_NAMES, "softmax": SOFTMAX}
-MIN_CLASSES, MAX_CLASSES = 2, 8  # csrc/kernels/launchers.h kSoftmaxMaxClasses
+MIN_CLASSES, MAX_CLASSES = 2, 8  # csrc/kernels/launchers.h kMinBlocks / kMaxBlocks
 
 
 def is_multiclass(kind: int) -> bool:

@@ -34,22 +34,8 @@ def combine_update_blocks(msgs: Sequence[torch.Tensor], coefs: Sequence[float], 
     """combine_update for a model of ``len(decay)`` blocks of ``block_ld`` columns (``d_x`` of them data) with their
     own (decay, gm, l2): a multi-model run (ops/multimodel.py).  Block k gets exactly what ``combine_update`` gives
     that block alone; padding columns stay zero."""
-    M = len(decay)
-    if not (len(gm) == M and len(l2) == M and beta.numel() == M * block_ld and 1 <= d_x <= block_ld):
-        raise ValueError(f"combine_update_blocks: {M} blocks of {block_ld} columns do not describe this model")
-    if beta.is_cuda:
-        C = native()
-        if len(msgs) > C.MAX_MSGS:
-            raise ValueError(f"at most {C.MAX_MSGS} messages per combine")
-        C.combine_update_blocks(list(msgs), [float(c) for c in coefs], beta, u, hist, beta_w, g_out, int(block_ld),
-                                int(d_x), [float(x) for x in decay], [float(x) for x in gm], [float(x) for x in l2],
-                                float(theta), int(rule))
-        return
-    for k in range(M):
-        s = slice(k * block_ld, (k + 1) * block_ld)
-        _update_torch([m[s] for m in msgs], coefs, beta[s], u[s], d_x, decay[k], gm[k], l2[k], theta, rule,
-                      None if hist is None else hist[s], None if beta_w is None else beta_w[s],
-                      None if g_out is None else g_out[s])
+    _update_blocked("combine_update_blocks", msgs, coefs, beta, u, block_ld, d_x, decay, gm, l2, None, theta, rule,
+                    hist, beta_w, g_out)
 
 
 def combine_update_prox(msgs: Sequence[torch.Tensor], coefs: Sequence[float], beta: torch.Tensor, u: torch.Tensor,
@@ -59,25 +45,32 @@ def combine_update_prox(msgs: Sequence[torch.Tensor], coefs: Sequence[float], be
     """combine_update_blocks followed by the proximal step of an L1 penalty: block k's new beta is
     ``S_t(x) = |x| <= t ? +0.0 : x - copysign(t, x)`` of the updated x with t = ``thr[k]``, and the AGD momentum is
     formed from the thresholded beta.  A single model is one block (``block_ld = ld``, ``d_x = d``)."""
+    _update_blocked("combine_update_prox", msgs, coefs, beta, u, block_ld, d_x, decay, gm, l2, thr, theta, rule,
+                    hist, beta_w, g_out)
+
+
+def _update_blocked(name, msgs, coefs, beta, u, block_ld, d_x, decay, gm, l2, thr, theta, rule, hist, beta_w,
+                    g_out) -> None:
+    """The two blocked forms: ``thr`` None is combine_update_blocks, a sequence is combine_update_prox."""
     M = len(decay)
-    if not (1 <= M and len(gm) == M and len(l2) == M and len(thr) == M and beta.numel() == M * block_ld
-            and 1 <= d_x <= block_ld):
-        raise ValueError(f"combine_update_prox: {M} blocks of {block_ld} columns do not describe this model")
-    if not all(float(t) >= 0.0 for t in thr):
-        raise ValueError(f"combine_update_prox: thresholds must be >= 0 and not NaN, got {list(thr)}")
+    if not ((thr is None or (1 <= M and len(thr) == M)) and len(gm) == M and len(l2) == M
+            and beta.numel() == M * block_ld and 1 <= d_x <= block_ld):
+        raise ValueError(f"{name}: {M} blocks of {block_ld} columns do not describe this model")
+    if thr is not None and not all(float(t) >= 0.0 for t in thr):
+        raise ValueError(f"{name}: thresholds must be >= 0 and not NaN, got {list(thr)}")
     if beta.is_cuda:
         C = native()
         if len(msgs) > C.MAX_MSGS:
             raise ValueError(f"at most {C.MAX_MSGS} messages per combine")
-        C.combine_update_prox(list(msgs), [float(c) for c in coefs], beta, u, hist, beta_w, g_out, int(block_ld),
-                              int(d_x), [float(x) for x in decay], [float(x) for x in gm], [float(x) for x in l2],
-                              [float(x) for x in thr], float(theta), int(rule))
+        coefs_k = [[float(x) for x in v] for v in ((decay, gm, l2) if thr is None else (decay, gm, l2, thr))]
+        getattr(C, name)(list(msgs), [float(c) for c in coefs], beta, u, hist, beta_w, g_out, int(block_ld), int(d_x),
+                         *coefs_k, float(theta), int(rule))
         return
     for k in range(M):
         s = slice(k * block_ld, (k + 1) * block_ld)
         _update_torch([m[s] for m in msgs], coefs, beta[s], u[s], d_x, decay[k], gm[k], l2[k], theta, rule,
                       None if hist is None else hist[s], None if beta_w is None else beta_w[s],
-                      None if g_out is None else g_out[s], thr=float(thr[k]))
+                      None if g_out is None else g_out[s], thr=None if thr is None else float(thr[k]))
 
 
 def _soft_threshold(x: torch.Tensor, t: float) -> torch.Tensor:

@@ -1,6 +1,7 @@
 """GradLauncher.launch checks its operands on the host (csrc/runtime/grad_launcher.h check_operands): a G with
 too few rows, a G or beta of the wrong dtype and a beta shorter than ld raise before anything is enqueued, for a
-dense, a softmax and a sparse plan; GradLauncher.dense rejects a dtype code outside 0..2 (GPU only)."""
+dense, a softmax and a sparse plan; GradLauncher.dense rejects a dtype code outside 0..2; GradLauncher.softmax and
+GradLauncher.multimodel reject a task table that points outside its segments, rows or slab (GPU only)."""
 import numpy as np
 import pytest
 import scipy.sparse as sps
@@ -8,6 +9,7 @@ import torch
 
 from erasurehead_amd.models.losses import SQUARED_HINGE
 from erasurehead_amd.ops import DenseGradPlan, SparseGradPlan, get_precision
+from erasurehead_amd.ops.grad import _SEG
 from erasurehead_amd.ops.softmax import SoftmaxGradPlan
 
 pytestmark = pytest.mark.gpu
@@ -80,3 +82,43 @@ def test_dense_plan_rejects_unknown_dtype_code(native):
     plan.native_launcher().launch(torch.ones(plan.ld, dtype=PREC.acc, device=DEV), G)
     torch.cuda.synchronize()
     assert not torch.any(G[:, :D] == 123.0)
+
+
+# One 8-row segment, two tasks (rows 0-4 and 4-8, slab rows 0 and 1), one partition; d_x = 5, ld_x = 6, two blocks.
+BLOCKS, DX, LDX = 2, 5, 6
+TASKS = [(0, 0, 0, 4, 0), (0, 0, 4, 8, 1)]  # (slot, segment, row_begin, row_end, slab row)
+BAD_TABLES = {
+    "valid": (TASKS, [0, 2], 0, False),
+    "segment index 1": ([(0, 1, 0, 4, 0), TASKS[1]], [0, 2], 0, True),
+    "row_end 9": ([TASKS[0], (0, 0, 4, 9, 1)], [0, 2], 0, True),
+    "row_begin > row_end": ([(0, 0, 5, 4, 0), TASKS[1]], [0, 2], 0, True),
+    "slab row 2": ([TASKS[0], (0, 0, 4, 8, 2)], [0, 2], 0, True),
+    "part_task_begin [0, 1]": (TASKS, [0, 1], 0, True),
+    "part_task_begin [1, 2]": (TASKS, [1, 2], 0, True),
+    "slab one element short": (TASKS, [0, 2], 1, True),
+}
+
+
+@pytest.mark.parametrize("kind", ["softmax", "multimodel"])
+@pytest.mark.parametrize("case", list(BAD_TABLES))
+def test_blocked_plans_check_their_task_table_on_the_host(kind, case, native):
+    """Only constructs launchers: nothing is launched.  The kernels index segments, rows and slab rows with the
+    table, so a table that leaves them has to be an error at plan time, for both blocked plans."""
+    tasks, begin, short, bad = BAD_TABLES[case]
+    X = torch.zeros((8, LDX), dtype=torch.float64, device=DEV)
+    y = torch.zeros(8, dtype=torch.float64, device=DEV)
+    segs = torch.tensor(list(_SEG.pack(X.data_ptr(), y.data_ptr(), 1.0, 8)), dtype=torch.uint8).to(DEV)
+    tt = torch.tensor(tasks, dtype=torch.int32, device=DEV)
+    ptb = torch.tensor(begin, dtype=torch.int32, device=DEV)
+    slab = torch.zeros(len(tasks) * 4 * BLOCKS * LDX - short, dtype=torch.float64, device=DEV)
+
+    def make():
+        if kind == "softmax":
+            return native.GradLauncher.softmax(0, BLOCKS, segs, tt, slab, ptb, DX, LDX)
+        return native.GradLauncher.multimodel(0, 0, BLOCKS, segs, tt, slab, ptb, DX, LDX)
+
+    if bad:
+        with pytest.raises(ValueError):
+            make()
+    else:
+        assert make() is not None

@@ -318,6 +318,24 @@ def test_plan_constructor_checks():
         SparseGradPlan(msgs, {}, prec, losses.SOFTMAX, 6)
 
 
+def test_blocked_plans_reject_a_non_contiguous_y():
+    """Both kernels read y with raw LDS-DMA, so both plans require it contiguous and name the partition."""
+    from erasurehead_amd.ops.multimodel import MultiModelGradPlan
+
+    prec = get_precision("fp64")
+    X = torch.zeros((10, 6), dtype=torch.float64)
+    y = torch.zeros(20, dtype=torch.float64)[::2]  # ten valid labels for either plan, stride 2
+    assert not y.is_contiguous()
+    msgs, parts = [[(0, 1.0)]], {0: (X, y)}
+    with pytest.raises(ValueError, match="partition 0"):
+        SoftmaxGradPlan(msgs, parts, prec, 3, 6)
+    with pytest.raises(ValueError, match="partition 0"):
+        MultiModelGradPlan(msgs, parts, prec, losses.LOGISTIC, 3, 6)
+    parts = {0: (X, y.contiguous())}  # the same data, contiguous: both construct
+    assert SoftmaxGradPlan(msgs, parts, prec, 3, 6).nslots == 1
+    assert MultiModelGradPlan(msgs, parts, prec, losses.LOGISTIC, 3, 6).nslots == 1
+
+
 def test_plan_on_cpu_tensors_is_the_oracle():
     prec = get_precision("fp64")
     rng = np.random.RandomState(8)

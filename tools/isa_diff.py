@@ -1,6 +1,6 @@
 """Compare the gfx950 kernels of two builds, symbol by symbol (CPU only; nothing is loaded or run).
 
-    python tools/isa_diff.py PARENT TREE [--show NAME_PART] [--vmem NAME_PART]
+    python tools/isa_diff.py PARENT TREE [--show NAME_PART] [--vmem NAME_PART] [--rename OLD=NEW ...]
 
 PARENT and TREE are two built libraries (``erasurehead_amd/_C*.so``), two fat objects (``build/objs/*.hip.o``)
 or two bare gfx950 code objects.  Every mangled kernel name is disassembled with ``llvm-objdump -d
@@ -15,6 +15,10 @@ exactly when their instruction streams are the same text.  Printed:
 ``--show PART`` also prints a unified diff of the differing symbols whose name contains PART; ``--vmem PART``
 prints, for those, the sequence of vector-memory instructions, wait counts and barriers of each side, which is
 what decides whether a row loop still waits for one row while the prefetched ones stay in flight.
+
+``--rename OLD=NEW`` (repeatable) applies ``re.sub(OLD, NEW)`` to the demangled names of the parent's symbols the
+tree lacks and compares each with the tree symbol of that name, so a renamed kernel is compared instead of being
+listed on both sides, e.g. ``--rename 'old_reduce<(\w+)>=new_reduce<\1>'``.
 
 This is the recipe docs/PERF_NOTES.md applies to every "nothing may move" refactor.  The exit status is 0
 whether or not anything differs: the tool reports, the reader judges.
@@ -95,6 +99,29 @@ def load(path: str, work: str):
     return kernels, meta
 
 
+def demangle(names):
+    tool = shutil.which("llvm-cxxfilt", path=LLVM) or shutil.which("c++filt")
+    if tool is None:
+        sys.exit("--rename needs llvm-cxxfilt or c++filt")
+    out = subprocess.run([tool], input="\n".join(names), capture_output=True, text=True, check=True).stdout
+    return dict(zip(names, out.splitlines()))
+
+
+def renamed(parent, tree, renames):
+    """{parent symbol: tree symbol} for the parent's symbols that are the tree's once every OLD=NEW (a regular
+    expression and its replacement) is applied to their demangled names."""
+    da, db = demangle(sorted(set(parent) - set(tree))), demangle(sorted(set(tree) - set(parent)))
+    by_name = {d: n for n, d in db.items()}
+    res = {}
+    for n, d in da.items():
+        for r in renames:
+            old, new = r.split("=", 1)
+            d = re.sub(old, new, d)
+        if d in by_name:
+            res[n] = by_name[d]
+    return res
+
+
 def histogram_delta(a, b):
     ha = collections.Counter(l.split()[0] for l in a)
     hb = collections.Counter(l.split()[0] for l in b)
@@ -107,33 +134,39 @@ def main(argv=None):
     ap.add_argument("tree")
     ap.add_argument("--show", default=None, help="print a unified diff of differing symbols containing this text")
     ap.add_argument("--vmem", default=None, help="print the vector-memory / wait / barrier sequence of those")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW",
+                    help="compare a renamed kernel: re.sub(OLD, NEW) on the parent's demangled names (repeatable)")
     a = ap.parse_args(argv)
     with tempfile.TemporaryDirectory() as wa, tempfile.TemporaryDirectory() as wb:
         ka, ma = load(a.parent, wa)
         kb, mb = load(a.tree, wb)
+    ren = renamed(ka, kb, a.rename) if a.rename else {}
     print(f"kernel symbols: parent {len(ka)}, tree {len(kb)}")
-    for title, names in (("only in parent", sorted(set(ka) - set(kb))), ("only in tree", sorted(set(kb) - set(ka)))):
+    for title, names in (("only in parent", sorted(set(ka) - set(kb) - set(ren))),
+                         ("only in tree", sorted(set(kb) - set(ka) - set(ren.values())))):
         print(f"{title}: {len(names)}")
         for n in names:
             print("   ", n)
-    both = sorted(set(ka) & set(kb))
-    differ = [n for n in both if ka[n] != kb[n] or ma[n] != mb[n]]
-    print(f"identical: {len(both) - len(differ)} of {len(both)} common symbols; differing: {len(differ)}")
-    for n in differ:
-        print(f"\n{n}")
-        print(f"    instructions {len(ka[n])} -> {len(kb[n])}")
-        print("    " + ", ".join(f"{k} {ma[n][k]} -> {mb[n][k]}" for k in NOTE_KEYS))
-        delta = histogram_delta(ka[n], kb[n])
+    if ren:
+        print(f"renamed: {len(ren)} parent symbols compared with {len(set(ren.values()))} of the tree")
+    pairs = [(n, n) for n in sorted(set(ka) & set(kb))] + sorted(ren.items())  # (parent symbol, tree symbol)
+    differ = [(p, t) for p, t in pairs if ka[p] != kb[t] or ma[p] != mb[t]]
+    print(f"identical: {len(pairs) - len(differ)} of {len(pairs)} common symbols; differing: {len(differ)}")
+    for p, n in differ:
+        print(f"\n{n}" if p == n else f"\n{p} -> {n}")
+        print(f"    instructions {len(ka[p])} -> {len(kb[n])}")
+        print("    " + ", ".join(f"{k} {ma[p][k]} -> {mb[n][k]}" for k in NOTE_KEYS))
+        delta = histogram_delta(ka[p], kb[n])
         print("    opcodes: " + (", ".join(f"{op} {d:+d}" for op, d in delta.items()) or "same histogram, other order"))
         if a.vmem is not None and a.vmem in n:
-            for side, body in (("parent", ka[n]), ("tree", kb[n])):
+            for side, body in (("parent", ka[p]), ("tree", kb[n])):
                 print(f"    -- {side}: vector memory, waits, barriers")
                 for l in body:
                     if FLOW.match(l):
                         print("      ", l)
         if a.show is not None and a.show in n:
             sys.stdout.writelines(l if l.endswith("\n") else l + "\n"
-                                  for l in difflib.unified_diff(ka[n], kb[n], "parent", "tree", lineterm="", n=2))
+                                  for l in difflib.unified_diff(ka[p], kb[n], "parent", "tree", lineterm="", n=2))
     return 0
 
 
