@@ -255,7 +255,12 @@ __device__ __forceinline__ double readlane_a(double x, int l) {
 //     (continuous in z, so one fmax form serves the per-row, the branch-free and the hardware variants)
 //   softmax (multi-class, labels = class indices): its own kernel (grad_softmax.hip); the code is listed
 //     here for documentation only -- no scalar-residual kernel can run it, so dispatch_loss rejects it
-enum LossKind : int { kLogistic = 0, kLeastSquares = 1, kSquaredHinge = 2, kSoftmax = 3 };
+//   weighted logistic / squared hinge: the label carries the row's weight, y~ = s * w with the class s the sign
+//     BIT of y~ (so -0.0 is a negative row of weight 0) and w = |y~| >= 0.  With t = s z:
+//       r = -(c y~) sigmoid(-t)   and   r = -2 (c y~) max(0, 1 - t)
+//     For y~ = +-1, t is exactly y z, so these are bitwise the unweighted forms; a zero weight gives r = +-0.
+enum LossKind : int { kLogistic = 0, kLeastSquares = 1, kSquaredHinge = 2, kSoftmax = 3, kLogisticW = 4,
+                      kSquaredHingeW = 5 };
 
 // Runtime loss code -> compile-time LOSS.  f is called with a std::integral_constant<int, LOSS> and
 // returns a hipError_t; an unknown code launches nothing.  Every launcher dispatches through this, so
@@ -267,6 +272,8 @@ inline hipError_t dispatch_loss(int loss, F&& f) {
     case kLogistic: return f(std::integral_constant<int, kLogistic>{});
     case kLeastSquares: return f(std::integral_constant<int, kLeastSquares>{});
     case kSquaredHinge: return f(std::integral_constant<int, kSquaredHinge>{});
+    case kLogisticW: return f(std::integral_constant<int, kLogisticW>{});
+    case kSquaredHingeW: return f(std::integral_constant<int, kSquaredHingeW>{});
     default: return hipErrorInvalidValue;
   }
 }
@@ -286,6 +293,10 @@ inline hipError_t dispatch_storage(int dtype, F&& f) {
     default: return hipErrorInvalidValue;
   }
 }
+
+// Weighted codes: s z, with the class s the sign bit of the weighted label.
+template <typename A>
+__device__ __forceinline__ A signed_margin(A y, A z) { return signbit(y) ? -z : z; }
 
 template <typename A>
 __device__ __forceinline__ A sigmoid_neg(A t) {
@@ -313,6 +324,10 @@ __device__ __forceinline__ float residual_hw(float z, float y, float coef) {
     return -(coef * y) * sigmoid_neg_hw(y * z);
   } else if constexpr (LOSS == kSquaredHinge) {
     return -2.f * (coef * y) * fmaxf(0.f, 1.f - y * z);
+  } else if constexpr (LOSS == kLogisticW) {
+    return -(coef * y) * sigmoid_neg_hw(signed_margin(y, z));
+  } else if constexpr (LOSS == kSquaredHingeW) {
+    return -2.f * (coef * y) * fmaxf(0.f, 1.f - signed_margin(y, z));
   } else {
     return -2.f * coef * (y - z);
   }
@@ -328,6 +343,13 @@ __device__ __forceinline__ A residual_branchfree(A z, A y, A coef) {
     return -(coef * y) * (t > A(0) ? e * q : q);
   } else if constexpr (LOSS == kSquaredHinge) {
     return A(-2) * (coef * y) * fmax(A(0), A(1) - y * z);
+  } else if constexpr (LOSS == kLogisticW) {
+    const A t = signed_margin(y, z);
+    const A e = exp(-fabs(t));
+    const A q = A(1) / (A(1) + e);
+    return -(coef * y) * (t > A(0) ? e * q : q);
+  } else if constexpr (LOSS == kSquaredHingeW) {
+    return A(-2) * (coef * y) * fmax(A(0), A(1) - signed_margin(y, z));
   } else {
     return A(-2) * coef * (y - z);
   }
@@ -339,13 +361,18 @@ __device__ __forceinline__ A residual(A z, A y, A coef) {
     return -(coef * y) * sigmoid_neg<A>(y * z);
   } else if constexpr (LOSS == kSquaredHinge) {
     return A(-2) * (coef * y) * fmax(A(0), A(1) - y * z);
+  } else if constexpr (LOSS == kLogisticW) {
+    return -(coef * y) * sigmoid_neg<A>(signed_margin(y, z));
+  } else if constexpr (LOSS == kSquaredHingeW) {
+    return A(-2) * (coef * y) * fmax(A(0), A(1) - signed_margin(y, z));
   } else {
     return A(-2) * coef * (y - z);
   }
 }
 
 // Per-element loss of the evaluation epilogues (label y, prediction p, both widened to fp64):
-//   logistic log(1 + exp(-y p)) (stable form), least squares (y - p)^2, squared hinge max(0, 1 - y p)^2.
+//   logistic log(1 + exp(-y p)) (stable form), least squares (y - p)^2, squared hinge max(0, 1 - y p)^2;
+//   the weighted codes w times the logistic / squared-hinge loss of (s, p), w = |y| and s the sign bit of y.
 template <int LOSS>
 __device__ __forceinline__ double loss_value(double y, double p) {
   if constexpr (LOSS == kLogistic) {
@@ -354,6 +381,12 @@ __device__ __forceinline__ double loss_value(double y, double p) {
   } else if constexpr (LOSS == kSquaredHinge) {
     const double m = fmax(0.0, 1.0 - y * p);
     return m * m;
+  } else if constexpr (LOSS == kLogisticW) {
+    const double m = -signed_margin(y, p);
+    return fabs(y) * ((m > 0.0 ? m : 0.0) + log1p(exp(-fabs(m))));
+  } else if constexpr (LOSS == kSquaredHingeW) {
+    const double m = fmax(0.0, 1.0 - signed_margin(y, p));
+    return fabs(y) * (m * m);
   } else {
     const double e = y - p;
     return e * e;

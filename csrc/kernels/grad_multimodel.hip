@@ -161,18 +161,24 @@ hipError_t grad_models_launch(int dtype, int loss, int models, const void* segs,
     if constexpr (std::is_same_v<T, bf16_t>) {
       return hipErrorInvalidValue;
     } else {
-      return dispatch_loss(loss, [&](auto L) {
+      return dispatch_loss(loss, [&](auto L) -> hipError_t {
         constexpr int LOSS = decltype(L)::value;
-        const int rowbytes = ld_x * static_cast<int>(sizeof(T));
-        const int srows = blocks_stage_rows(rowbytes);
-        const size_t lds = blocks_ring_bytes(srows, rowbytes);
-        auto launch = [&](auto kern) {
-          return launch_blocks<A>(kern, lds, srows, models, segs, tasks, ntasks, part_task_begin, nparts, beta, slab,
-                                  Gb, d_x, ld_x, st, gate);
-        };
-        return ld_x <= 256   ? launch(grad_models<T, A, 4, LOSS>)
-               : ld_x <= 512 ? launch(grad_models<T, A, 8, LOSS>)
-                             : launch(grad_models<T, A, 16, LOSS>);
+        // the weighted codes (kLogisticW, kSquaredHingeW) have no multi-model instance: the range check above
+        // rejects them, and nothing is instantiated for them here
+        if constexpr (LOSS > kSquaredHinge) {
+          return hipErrorInvalidValue;
+        } else {
+          const int rowbytes = ld_x * static_cast<int>(sizeof(T));
+          const int srows = blocks_stage_rows(rowbytes);
+          const size_t lds = blocks_ring_bytes(srows, rowbytes);
+          auto launch = [&](auto kern) {
+            return launch_blocks<A>(kern, lds, srows, models, segs, tasks, ntasks, part_task_begin, nparts, beta,
+                                    slab, Gb, d_x, ld_x, st, gate);
+          };
+          return ld_x <= 256   ? launch(grad_models<T, A, 4, LOSS>)
+                 : ld_x <= 512 ? launch(grad_models<T, A, 8, LOSS>)
+                               : launch(grad_models<T, A, 16, LOSS>);
+        }
       });
     }
   });

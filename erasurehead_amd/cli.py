@@ -52,6 +52,12 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--l1s", type=parse_float_list, default=None, metavar="L1,L2,...",
                    help="sweep: one model per L1 strength (a regularisation path in one run; zipped with --alphas / "
                         "--lrs, a single value is broadcast)")
+    g.add_argument("--class-weight", default=None, metavar="balanced|P:N",
+                   help="logistic / squared hinge: weights of the +1 and the -1 class, P:N, or balanced = n / (2 n_c) "
+                        "over the training labels; test rows take them too")
+    g.add_argument("--sample-weights", default=None, metavar="PATH",
+                   help="logistic / squared hinge: a file in label.dat's format and length, entry i the weight (>= 0) "
+                        "of training label i; multiplies with --class-weight")
     g.add_argument("--seed", type=int, default=None)
     g.add_argument("--data", default="files", choices=["files", "synthetic"])
     g.add_argument("--data-seed", type=int, default=0)
@@ -143,7 +149,8 @@ def parse(argv: List[str]):
                     tie_break=a.tie_break, tie_seed=a.tie_seed, shard=a.shard,
                     integrity=not a.no_integrity, delay_on=a.delay_on, slow_ranks=parse_slow_ranks(a.slow_ranks),
                     dedicated_master=a.dedicated_master, device_records=a.device_records,
-                    sweep_alpha=a.alphas, sweep_lr=a.lrs, l1=a.l1, sweep_l1=a.l1s)
+                    sweep_alpha=a.alphas, sweep_lr=a.lrs, l1=a.l1, sweep_l1=a.l1s,
+                    class_weight=a.class_weight, sample_weights=a.sample_weights)
     return cfg, a
 
 

@@ -20,6 +20,20 @@ import numpy as np
 SWEEP_MIN_MODELS, SWEEP_MAX_MODELS = 2, 8  # csrc/kernels/launchers.h kMinBlocks / kMaxBlocks
 
 
+def parse_class_weight(spec):
+    """--class-weight: None, "balanced", or the weights (P, N) of the +1 and the -1 class from "P:N" / a pair."""
+    if spec is None or spec == "balanced":
+        return spec
+    try:
+        p, n = spec.split(":") if isinstance(spec, str) else spec
+        p, n = float(p), float(n)
+    except (TypeError, ValueError):
+        raise ValueError(f"--class-weight: expected 'balanced' or P:N (two positive numbers), got {spec!r}") from None
+    if not (np.isfinite(p) and np.isfinite(n) and p > 0 and n > 0):
+        raise ValueError(f"--class-weight: P and N must be finite and > 0, got {spec!r}")
+    return (p, n)
+
+
 @dataclass
 class RunConfig:
     n_procs: int
@@ -58,6 +72,12 @@ class RunConfig:
     # sweep, zipped with sweep_alpha / sweep_lr under the same rules; alone it makes a sweep of len(sweep_l1) models.
     l1: float = 0.0
     sweep_l1: Optional[List[float]] = None
+    # Row weights of the +-1-label losses (logistic, squared hinge): the labels carry them to the kernels
+    # (data/source.py WeightedSource, csrc/kernels/common.h kLogisticW / kSquaredHingeW).  class_weight: "balanced"
+    # (n / (2 n_c) over the training labels) or "P:N" / (P, N), the weights of the +1 and the -1 class;
+    # sample_weights: a file in label.dat's format and length, entry i the weight of label i.  The two multiply.
+    class_weight: Optional[object] = None
+    sample_weights: Optional[str] = None
     seed: Optional[int] = None  # beta_0 / B matrix seed (reference: unseeded)
     data: str = "files"  # files | synthetic (on-device generator, no files)
     data_seed: int = 0
@@ -141,6 +161,12 @@ class RunConfig:
         if not (np.isfinite(self.l1) and self.l1 >= 0):
             raise ValueError(f"l1 must be a finite value >= 0, got {self.l1}")
         self.sweep()  # the sweep's limits, each a ValueError that names it
+        self.class_weight = parse_class_weight(self.class_weight)
+        if self.weighted and self.loss in ("least_squares", "softmax"):
+            raise ValueError(f"--class-weight / --sample-weights: not supported with --loss {self.loss} (the label "
+                             f"cannot carry the weight there); logistic or squared_hinge")
+        if self.sample_weights is not None and self.data == "synthetic":
+            raise ValueError("--sample-weights: not with --data synthetic (there is no label.dat the file could match)")
 
     def _sweep_lists(self) -> Optional[Tuple[List[float], List[float], List[float]]]:
         """([alpha_k], [lr_k], [l1_k]) of a sweep run, every list broadcast to the M models; None without a list."""
@@ -194,6 +220,11 @@ class RunConfig:
             return None
         return np.stack([dataclasses.replace(self, lr=lr, sweep_alpha=None, sweep_lr=None, sweep_l1=None).eta()[: self.num_itrs]
                          for _, lr in sw])
+
+    @property
+    def weighted(self) -> bool:
+        """The run names class or sample weights (an ArraySource may still bring sample weights of its own)."""
+        return self.class_weight is not None or self.sample_weights is not None
 
     @property
     def tie_seed_value(self) -> int:

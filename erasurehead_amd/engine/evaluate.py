@@ -17,6 +17,10 @@ Runs with an L1 penalty (--l1 / --l1s, some lambda > 0) also report sparsity: ``
 data columns of every iterate) and ``l1_penalty`` are filled for every run; with some lambda > 0 the console gets
 one line ``>> L1: l1 = ..., nnz = k of d`` per model, the ``>> Model k:`` line of a sweep names ``l1``, and an
 ``nnz`` result file is written next to the ``auc`` file, under the same prefixes.
+Weighted runs (--class-weight / --sample-weights): training and test loss are the weighted means (1/n) sum w_i l_i
+with n the row count (test rows take the class weights), the AUC is the ordinary unweighted ROC AUC on the classes,
+the console gets one line ``>> Weights: class_weight = ..., w+ = ..., w- = ..., sum w / n = ...`` before the usual
+ones, and the result names carry the prefix ``weighted_`` (after ``sweep{k}_``, before ``sqhinge_``).
 """
 from __future__ import annotations
 
@@ -27,14 +31,15 @@ import numpy as np
 import torch
 
 from ..data import io as dio
-from ..models.losses import SQUARED_HINGE, is_classification, is_multiclass
-from ..ops.eval import auc_columns, loss_sums, predictions, predictions_and_loss
+from ..models.losses import SQUARED_HINGE, base_kind, is_classification, is_multiclass
+from ..ops.eval import auc_columns, loss_sums, predictions, predictions_and_loss, sign_labels
 from ..utils import report
 from .trainer import TrainResult, Trainer
 
 
 SQHINGE_PREFIX = "sqhinge_"  # result files of squared-hinge runs (next to the logistic names)
 SOFTMAX_PREFIX = "softmax_"
+WEIGHTED_PREFIX = "weighted_"  # result files of runs with class / sample weights
 SOFTMAX_P_ELEMS = 1 << 26  # logits held at once by the softmax evaluation (rounds are chunked to fit)
 
 
@@ -77,6 +82,23 @@ def _write_nnz(files: Dict[str, str], nnz, key: str = "nnz") -> None:
     head, tail = files[auc_key].rsplit("auc", 1)
     files[key] = head + "nnz" + tail
     dio.save_vector(np.asarray(nnz, dtype=np.float64), files[key])
+
+
+def _weights_line(trainer: Trainer) -> str:
+    cw = trainer.cfg.class_weight
+    spec = "none" if cw is None else cw if isinstance(cw, str) else "%g:%g" % tuple(cw)
+    return ">> Weights: class_weight = %s, w+ = %g, w- = %g, sum w / n = %g" % (
+        spec, trainer.class_weight[0], trainer.class_weight[1], trainer.weight_sum_over_n)
+
+
+def _result_names(trainer: Trainer) -> Dict[str, str]:
+    """The scheme's result names under the loss's prefixes: ``weighted_`` first, then ``sqhinge_``."""
+    names = trainer.scheme.output_names(trainer.cfg.fix_quirks)
+    if base_kind(trainer.loss) == SQUARED_HINGE:
+        names = {k: SQHINGE_PREFIX + v for k, v in names.items()}
+    if getattr(trainer, "weighted", False):
+        names = {k: WEIGHTED_PREFIX + v for k, v in names.items()}
+    return names
 
 
 def eval_partitions(trainer: Trainer):
@@ -168,7 +190,10 @@ def _evaluate_sweep(trainer: Trainer, res: TrainResult, log, write: bool) -> Eva
     R = res.betaset.shape[0]
     B = torch.from_numpy(np.ascontiguousarray(res.betaset)).to(dev).reshape(R * M, ld_x)
     parts = eval_partitions(trainer)
+    weighted = getattr(trainer, "weighted", False)
     if cfg.verbose:
+        if weighted:
+            log(_weights_line(trainer))
         log(report.total_time_line(res.total_time))
         if trainer.scheme.logs_eval_loading and not trainer.source.is_sparse:
             for p in parts:
@@ -180,7 +205,8 @@ def _evaluate_sweep(trainer: Trainer, res: TrainResult, log, write: bool) -> Eva
     training_loss = (np.asarray(sums) / max(1, n_train)).reshape(R, M)
     testing_loss = (np.asarray(tsum) / max(1, n_test)).reshape(R, M)
     classify = is_classification(kind)
-    auc = (auc_columns(yt, P) if classify else np.zeros(R * M)).reshape(R, M)
+    # weighted runs: the classes behind the weighted labels (an unweighted AUC, comparable across runs)
+    auc = (auc_columns(sign_labels(yt) if weighted else yt, P) if classify else np.zeros(R * M)).reshape(R, M)
     nnz, pen = sparsity(trainer, res.betaset)
     files = None
     do_write = write and (classify or cfg.save_linear)
@@ -199,10 +225,7 @@ def _evaluate_sweep(trainer: Trainer, res: TrainResult, log, write: bool) -> Eva
             if trainer.prox and R:
                 log(_nnz_line(trainer.sweep_l1[k], nnz[-1, k], d_x))
         if do_write:
-            names = trainer.scheme.output_names(cfg.fix_quirks)
-            if kind == SQUARED_HINGE:
-                names = {key: SQHINGE_PREFIX + v for key, v in names.items()}
-            names = {key: sweep_prefix(k) + v for key, v in names.items()}
+            names = {key: sweep_prefix(k) + v for key, v in _result_names(trainer).items()}
             out = report.write_results(dio.results_dir(data_dir), names, training_loss[:, k], testing_loss[:, k],
                                        auc[:, k], res.timeset, res.worker_timeset, cfg.full_precision_outputs)
             files.update({sweep_prefix(k) + key: v for key, v in out.items()})
@@ -232,7 +255,10 @@ def evaluate(trainer: Trainer, res: TrainResult, log=None, write: bool = True) -
     B[:, :d] = torch.from_numpy(res.betaset).to(dev)
     kind = trainer.loss
     parts = eval_partitions(trainer)
+    weighted = getattr(trainer, "weighted", False)
     if cfg.verbose:
+        if weighted:
+            log(_weights_line(trainer))
         log(report.total_time_line(res.total_time))
         if trainer.scheme.logs_eval_loading and not trainer.source.is_sparse:
             for p in parts:
@@ -244,7 +270,8 @@ def evaluate(trainer: Trainer, res: TrainResult, log=None, write: bool = True) -
     training_loss = sums / max(1, n_train)
     testing_loss = tsum / max(1, n_test)
     classify = is_classification(kind)
-    auc = auc_columns(yt, P) if classify else np.zeros(R)
+    # weighted runs: the classes behind the weighted labels (an unweighted AUC, comparable across runs)
+    auc = auc_columns(sign_labels(yt) if weighted else yt, P) if classify else np.zeros(R)
     nnz, pen = sparsity(trainer, res.betaset)
     if cfg.verbose:
         for i in range(R):
@@ -256,9 +283,7 @@ def evaluate(trainer: Trainer, res: TrainResult, log=None, write: bool = True) -
             log(_nnz_line(cfg.l1, nnz[-1], d))
     files = None
     if write and (classify or cfg.save_linear):
-        names = trainer.scheme.output_names(cfg.fix_quirks)
-        if kind == SQUARED_HINGE:
-            names = {k: SQHINGE_PREFIX + v for k, v in names.items()}
+        names = _result_names(trainer)
         data_dir = getattr(trainer.source, "data_dir", None) or cfg.input_dir
         files = report.write_results(dio.results_dir(data_dir), names, training_loss, testing_loss, auc,
                                      res.timeset, res.worker_timeset, cfg.full_precision_outputs)

@@ -49,9 +49,10 @@ from .loops import LoopInputs, release_override, select_release_form, select_rou
 from ..codes.schemes import Arrival, Scheme, SchemeError, make_scheme, scheme_key
 from ..config import RunConfig
 from ..data import io as dio
-from ..data.source import DataSource, FileSource, SyntheticSource
-from ..models.losses import (LEAST_SQUARES, LOGISTIC, LOSS_CHOICES, SOFTMAX, UpdateRule, check_classes,
-                             is_classification)
+from ..data.source import (DataSource, FileSource, SyntheticSource, WeightedSource, balanced_class_weights,
+                           check_weights)
+from ..models.losses import (LEAST_SQUARES, LOGISTIC, LOSS_CHOICES, SOFTMAX, SQUARED_HINGE, UpdateRule, check_classes,
+                             is_classification, weighted_kind)
 from ..ops.grad import DenseGradPlan, SharedGradPlan, SparseGradPlan
 from ..ops.softmax import SoftmaxGradPlan
 from ..ops.multimodel import MultiModelGradPlan
@@ -177,6 +178,15 @@ class Trainer:
             if cfg.loss not in LOSS_CHOICES:
                 raise ValueError(f"unknown loss {cfg.loss!r}: auto or one of {sorted(LOSS_CHOICES)}")
             self.loss = LOSS_CHOICES[cfg.loss]
+        # class / sample weights: the labels carry them (data/source.py WeightedSource) and the plan runs the weighted
+        # code of the loss; without them the run takes exactly the code paths it takes without the feature
+        self.weighted = cfg.weighted or getattr(source, "weights", None) is not None
+        if self.weighted:
+            if self.loss not in (LOGISTIC, SQUARED_HINGE):
+                name = {LEAST_SQUARES: "least squares", SOFTMAX: "softmax"}.get(self.loss, str(self.loss))
+                raise ValueError(f"--class-weight / --sample-weights: not supported with the {name} loss (the label "
+                                 f"cannot carry the weight there); logistic or squared_hinge")
+            self.loss = weighted_kind(self.loss)
         # multi-class softmax: the model is [classes][ld_x] flattened (ops/softmax.py); 1 for every other loss
         self.classes = check_classes(cfg.classes or 2) if self.loss == SOFTMAX else 1
         # (alpha, lr) sweep: M models of one scalar loss, the model [M][ld_x] flattened (ops/multimodel.py)
@@ -251,6 +261,9 @@ class Trainer:
                 data_dir = dio.dataset_dir(cfg.input_dir, cfg.is_real, cfg.dataset, cfg.n_rows, cfg.n_cols)
                 data_dir = data_dir + sch.data_subdir()
                 source = FileSource(data_dir, cfg.is_real, sch.rows_per_partition, cfg.n_cols)
+        self.class_weight, self.weight_spec, self.weight_sum_over_n = None, None, None
+        if self.weighted:
+            source = self._weighted_source(source)
         self.source = source
         # d_x / ld_x: the data's columns and row stride; d / ld: everything model-sized (beta, messages,
         # history).  They differ only for softmax, whose model is the flattened [classes][ld_x].
@@ -271,6 +284,8 @@ class Trainer:
         t0 = time.perf_counter()
         parts = {p: source.partition(p, self.prec, dev) for p in needed}
         self.load_seconds = time.perf_counter() - t0
+        if self.weighted:
+            self._weight_sum(parts)
         segs = [m.segments for m in self.local_msgs]
 
         def make_plan(messages):
@@ -291,6 +306,56 @@ class Trainer:
         else:
             self.plan = make_plan(segs)
         self._parts = parts
+
+    def _weighted_source(self, source: DataSource) -> WeightedSource:
+        """Collective.  The run's source with the weights on its labels: --sample-weights read and checked against
+        label.dat, balanced class weights counted once by rank 0 over the training labels of every partition the run
+        uses and broadcast, so every rank multiplies with the same two numbers."""
+        cfg, env = self.cfg, self.env
+        sample = None
+        if cfg.sample_weights is not None:
+            if not isinstance(source, FileSource):
+                raise ValueError("--sample-weights: needs a file data source (an ArraySource takes weights= instead)")
+            # label.dat's format, but parsed exactly (the fast text reader of data/io.py may be an ulp off, which
+            # is nothing to a +-1 label and would change a weight and the checkpoint's hash of the vector)
+            raw = dio.load_vector_exact(cfg.sample_weights)
+            sample = check_weights(raw, len(source.labels()), f"--sample-weights {cfg.sample_weights}")
+        cw = cfg.class_weight
+        if cw == "balanced":
+            pair, err = None, None
+            if env.is_master or env.world == 1:
+                try:
+                    n_pos = n_neg = 0
+                    for p in range(self.scheme.n_partition_files):
+                        y = source.train_labels(p, env.device) if isinstance(source, SyntheticSource) \
+                            else source.train_labels(p)
+                        if bool(np.any((y != 1) & (y != -1))):
+                            raise ValueError("--class-weight balanced: needs labels in {-1, +1}")
+                        n_pos, n_neg = n_pos + int((y > 0).sum()), n_neg + int((y < 0).sum())
+                    pair = balanced_class_weights(n_pos, n_neg)
+                except ValueError as e:  # every rank raises it, none is left waiting in the broadcast
+                    err = str(e)
+            pair, err = env.broadcast_object((pair, err), 0) if env.world > 1 else (pair, err)
+            if err:
+                raise ValueError(err)
+            cw = pair
+        ws = WeightedSource(source, cw, sample)
+        self.class_weight = tuple(ws.class_weight or (1.0, 1.0))
+        # what a checkpoint stores and a resume must match (the numbers, not the way they were asked for)
+        self.weight_spec = {"class_weight": [float(x) for x in self.class_weight], "sample_sha256": ws.sample_sha256()}
+        return ws
+
+    def _weight_sum(self, parts) -> None:
+        """Collective.  sum w / n over the training rows of every partition some rank holds (1 = the weights keep
+        the scale of the unweighted objective, whose n stays the row count)."""
+        env = self.env
+        mine = {int(p): (float(abs(y).sum()), int(len(y))) for p, (_, y) in parts.items()}
+        every = env.broadcast_object(env.gather_objects(mine), 0) if env.world > 1 else [mine]
+        merged = {}
+        for x in every:
+            merged.update(x)
+        rows = sum(n for _, n in merged.values())
+        self.weight_sum_over_n = sum(w for w, _ in merged.values()) / max(1, rows)
 
     def _check_hbm(self, need_bytes: int) -> None:
         """Fail early (and say what to change) when this rank's resident partitions cannot fit."""
@@ -801,6 +866,8 @@ class Trainer:
         if self.models > 1:
             rep.update(models=self.models, sweep_alpha=list(self.sweep_alpha), sweep_lr=list(self.sweep_lr))
         rep.update(l1=list(self.sweep_l1) if self.models > 1 else float(self.cfg.l1), prox=bool(self.prox))
+        rep.update(weighted=bool(self.weighted), class_weight=list(self.class_weight) if self.weighted else None,
+                   weight_sum_over_n=self.weight_sum_over_n)
         rep.update({k: (round(float(v), 2) if isinstance(v, (int, float)) and not isinstance(v, bool) else v)
                     for k, v in self.rank_stats.items() if v is not None})
         kern = self._kernel_label()
@@ -1276,6 +1343,11 @@ class Trainer:
             if have_l1s != [float(x) for x in self.sweep_l1]:
                 raise ValueError(f"checkpoint {path} was written by a run with sweep_l1 = {have_l1s}; this run has "
                                  f"sweep_l1 = {list(self.sweep_l1)}")
+        # class / sample weights likewise; a checkpoint without the key was written by an unweighted run
+        have_w = st.get("weights")
+        if have_w != self.weight_spec:
+            raise ValueError(f"checkpoint {path} was written by a run with weights = {have_w}; this run has "
+                             f"weights = {self.weight_spec} (--class-weight / --sample-weights)")
         ld = self.ld
         if st["beta"].numel() != ld:
             raise ValueError("checkpoint beta has a different feature dimension")
@@ -1303,6 +1375,8 @@ class Trainer:
             state["sweep_lr"] = [float(x) for x in self.sweep_lr]
             state["sweep_l1"] = [float(x) for x in self.sweep_l1]
         state["l1"] = float(self.cfg.l1)
+        if self.weighted:
+            state["weights"] = self.weight_spec
         if getattr(self.scheme, "B", None) is not None:
             state["B"] = torch.from_numpy(np.ascontiguousarray(self.scheme.B, dtype=np.float64))
         tmp = path + ".tmp"

@@ -35,6 +35,12 @@ LOGISTIC = 0
 LEAST_SQUARES = 1
 SQUARED_HINGE = 2
 SOFTMAX = 3
+# weighted logistic / squared hinge (csrc/kernels/common.h kLogisticW / kSquaredHingeW): the label carries the row's
+# weight, y~ = s * w with the class s the sign BIT of y~ and w = |y~| >= 0.  The engine selects them when a run has
+# class or sample weights (engine/trainer.py); no --loss name maps to them.
+LOGISTIC_W = 4
+SQUARED_HINGE_W = 5
+_WEIGHTED = {LOGISTIC: LOGISTIC_W, SQUARED_HINGE: SQUARED_HINGE_W}
 LOSS_NAMES = {"logistic": LOGISTIC, "least_squares": LEAST_SQUARES, "squared_hinge": SQUARED_HINGE}
 # every loss a run can name (--loss): the per-row scalar losses above plus the multi-class model
 LOSS_CHOICES = {**LOSS_NAMES, "softmax": SOFTMAX}
@@ -54,7 +60,29 @@ def check_classes(classes: int) -> int:
 
 def is_classification(kind: int) -> bool:
     """Losses over labels in {-1, +1}: their runs are scored by ROC AUC and write result files."""
-    return kind in (LOGISTIC, SQUARED_HINGE)
+    return kind in (LOGISTIC, SQUARED_HINGE, LOGISTIC_W, SQUARED_HINGE_W)
+
+
+def weighted_kind(kind: int) -> int:
+    """The weighted code of a +-1-label loss: logistic -> LOGISTIC_W, squared hinge -> SQUARED_HINGE_W."""
+    if kind not in _WEIGHTED:
+        raise ValueError(f"loss kind {kind} has no weighted form (logistic and squared hinge only)")
+    return _WEIGHTED[kind]
+
+
+def base_kind(kind: int) -> int:
+    """The unweighted loss of a weighted code; every other code is its own base."""
+    return {w: k for k, w in _WEIGHTED.items()}.get(kind, kind)
+
+
+def is_weighted(kind: int) -> bool:
+    return kind in (LOGISTIC_W, SQUARED_HINGE_W)
+
+
+def split_weighted(y) -> Tuple[np.ndarray, np.ndarray]:
+    """(s, w) of weighted labels y~ = s * w: s = -1 where the sign bit is set (so at -0.0 too), else +1; w = |y~|."""
+    y = np.asarray(y, dtype=np.float64)
+    return np.where(np.signbit(y), -1.0, 1.0), np.abs(y)
 
 
 def _sigmoid_neg(t: np.ndarray) -> np.ndarray:
@@ -87,6 +115,24 @@ def squared_hinge_grad(X, y: np.ndarray, beta: np.ndarray, coef=None) -> np.ndar
     z = X.dot(beta)
     ymod = y if coef is None else coef * y
     r = -2.0 * ymod * np.maximum(0.0, 1.0 - y * z)
+    return np.asarray(X.T.dot(r)).ravel()
+
+
+def logistic_w_grad(X, y: np.ndarray, beta: np.ndarray, coef=None) -> np.ndarray:
+    """-X^T (coef*y~ / (exp(s * X beta) + 1)) with y~ = s * w."""
+    s, _ = split_weighted(y)
+    z = X.dot(beta)
+    ymod = y if coef is None else coef * y
+    r = -ymod * _sigmoid_neg(s * z)
+    return np.asarray(X.T.dot(r)).ravel()
+
+
+def squared_hinge_w_grad(X, y: np.ndarray, beta: np.ndarray, coef=None) -> np.ndarray:
+    """-2 X^T (coef*y~ * max(0, 1 - s * X beta)) with y~ = s * w."""
+    s, _ = split_weighted(y)
+    z = X.dot(beta)
+    ymod = y if coef is None else coef * y
+    r = -2.0 * ymod * np.maximum(0.0, 1.0 - s * z)
     return np.asarray(X.T.dot(r)).ravel()
 
 
@@ -159,7 +205,8 @@ def sweep_pack(B: np.ndarray, ld_x: int) -> np.ndarray:
     return out.reshape(B.shape[:-2] + (B.shape[-2] * ld_x,))
 
 
-_GRADS = {LOGISTIC: logistic_grad, LEAST_SQUARES: least_squares_grad, SQUARED_HINGE: squared_hinge_grad}
+_GRADS = {LOGISTIC: logistic_grad, LEAST_SQUARES: least_squares_grad, SQUARED_HINGE: squared_hinge_grad,
+          LOGISTIC_W: logistic_w_grad, SQUARED_HINGE_W: squared_hinge_w_grad}
 
 
 def worker_grad(kind: int, X, y, beta, coef=None) -> np.ndarray:
@@ -182,6 +229,21 @@ def squared_hinge_loss(y: np.ndarray, p: np.ndarray, n: Optional[int] = None) ->
     """(1/n) sum max(0, 1 - y p)^2."""
     m = np.maximum(0.0, 1.0 - np.asarray(y, dtype=np.float64) * np.asarray(p, dtype=np.float64))
     return float((m * m).sum() / (len(m) if n is None else n))
+
+
+def logistic_w_loss(y: np.ndarray, p: np.ndarray, n: Optional[int] = None) -> float:
+    """(1/n) sum w log(1 + exp(-s p)) over weighted labels y~ = s * w; n is the row count, not sum w."""
+    s, w = split_weighted(y)
+    m = -s * np.asarray(p, dtype=np.float64)
+    v = w * (np.maximum(m, 0.0) + np.log1p(np.exp(-np.abs(m))))
+    return float(v.sum() / (len(s) if n is None else n))
+
+
+def squared_hinge_w_loss(y: np.ndarray, p: np.ndarray, n: Optional[int] = None) -> float:
+    """(1/n) sum w max(0, 1 - s p)^2 over weighted labels y~ = s * w."""
+    s, w = split_weighted(y)
+    m = np.maximum(0.0, 1.0 - s * np.asarray(p, dtype=np.float64))
+    return float((w * m * m).sum() / (len(s) if n is None else n))
 
 
 def mse(y: np.ndarray, p: np.ndarray) -> float:

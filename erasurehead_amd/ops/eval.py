@@ -18,12 +18,24 @@ import numpy as np
 import torch
 
 from .._ext import native
-from ..models.losses import LEAST_SQUARES, LOGISTIC, SQUARED_HINGE
+from ..models.losses import LEAST_SQUARES, LOGISTIC, LOGISTIC_W, SQUARED_HINGE, SQUARED_HINGE_W
+
+
+def sign_labels(y: torch.Tensor) -> torch.Tensor:
+    """The classes of weighted labels y~ = s * w: +1 where the sign bit is clear, else -1 (so -0.0 is a negative
+    row of weight 0).  What auc_columns takes in a weighted run."""
+    return torch.where(torch.signbit(y), -torch.ones_like(y), torch.ones_like(y))
 
 
 def _loss_torch(kind: int, y: torch.Tensor, P: torch.Tensor) -> torch.Tensor:
     y = y.double()[:, None]
     P = P.double()
+    if kind in (LOGISTIC_W, SQUARED_HINGE_W):  # w * loss(s, p): the weight is |y~|, the class its sign bit
+        t = torch.where(torch.signbit(y), -P, P)
+        if kind == LOGISTIC_W:
+            return (y.abs() * (torch.clamp(-t, min=0) + torch.log1p(torch.exp(-t.abs())))).sum(0)
+        m = torch.clamp(1.0 - t, min=0)
+        return (y.abs() * (m * m)).sum(0)
     if kind == LOGISTIC:
         m = -y * P
         return (torch.clamp(m, min=0) + torch.log1p(torch.exp(-m.abs()))).sum(0)

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from .._ext import native
-from ..models.losses import LEAST_SQUARES, LOGISTIC, SOFTMAX, SQUARED_HINGE
+from ..models.losses import LEAST_SQUARES, LOGISTIC, LOGISTIC_W, SOFTMAX, SQUARED_HINGE, SQUARED_HINGE_W
 from .precision import Precision
 
 _SEG = struct.Struct("<QQdq")  # csrc Segment {const void* X; const void* y; double coef; long long nrows}
@@ -466,6 +466,11 @@ def _residual_torch(kind: int, z, y, coef):
         return -(coef * y) * torch.sigmoid(-(y * z))
     if kind == SQUARED_HINGE:
         return -2.0 * (coef * y) * torch.clamp(1.0 - y * z, min=0)
+    if kind in (LOGISTIC_W, SQUARED_HINGE_W):  # y = s * w: the class is the sign bit, for y = +-1 t is exactly y * z
+        t = torch.where(torch.signbit(y), -z, z)
+        if kind == LOGISTIC_W:
+            return -(coef * y) * torch.sigmoid(-t)
+        return -2.0 * (coef * y) * torch.clamp(1.0 - t, min=0)
     if kind != LEAST_SQUARES:
         raise ValueError(f"unknown loss kind {kind}")
     return -2.0 * coef * (y - z)
@@ -1188,6 +1193,10 @@ class SparseGradPlan:
                     r = -(c * y) * (1.0 / (1.0 + np.exp(np.clip(y * z, -700, 700))))
                 elif self.loss == SQUARED_HINGE:
                     r = -2.0 * (c * y) * np.maximum(0.0, 1.0 - y * z)
+                elif self.loss == LOGISTIC_W:  # y = s * w: the class is the sign bit
+                    r = -(c * y) * (1.0 / (1.0 + np.exp(np.clip(np.where(np.signbit(y), -z, z), -700, 700))))
+                elif self.loss == SQUARED_HINGE_W:
+                    r = -2.0 * (c * y) * np.maximum(0.0, 1.0 - np.where(np.signbit(y), -z, z))
                 elif self.loss == LEAST_SQUARES:
                     r = -2.0 * c * (y - z)
                 else:

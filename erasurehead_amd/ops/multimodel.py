@@ -12,14 +12,18 @@ from typing import Dict, Sequence, Tuple
 import torch
 
 from .._ext import native
-from ..models.losses import LEAST_SQUARES, LOGISTIC, SQUARED_HINGE
+from ..models.losses import LEAST_SQUARES, LOGISTIC, LOGISTIC_W, SQUARED_HINGE, SQUARED_HINGE_W, is_weighted
 from .blockplan import MAX_LD, SUBS, BlockGradPlan  # noqa: F401 (the plan's limits)
 from .grad import _residual_torch
 from .precision import Precision
 
 MIN_MODELS, MAX_MODELS = 2, 8  # csrc/kernels/launchers.h kMinBlocks / kMaxBlocks
 PRECISIONS = ("fp64", "fp32", "fp32x64")
-LOSSES = (LOGISTIC, LEAST_SQUARES, SQUARED_HINGE)
+LOSSES = (LOGISTIC, LEAST_SQUARES, SQUARED_HINGE, LOGISTIC_W, SQUARED_HINGE_W)  # the weighted codes: CPU tensors only
+
+# csrc/kernels/grad_multimodel.hip instantiates the three unweighted losses only
+NO_WEIGHTED_KERNEL = ("multi-model: --class-weight / --sample-weights in a sweep (--alphas / --lrs / --l1s) run on CPU "
+                      "tensors only: the multi-model GPU kernel has no weighted instance")
 
 
 class MultiModelGradPlan(BlockGradPlan):
@@ -39,6 +43,8 @@ class MultiModelGradPlan(BlockGradPlan):
         the trainer before it loads anything)."""
         if not MIN_MODELS <= int(models) <= MAX_MODELS:
             raise ValueError(f"multi-model: models must be in {MIN_MODELS}..{MAX_MODELS}, got {models}")
+        if is_weighted(loss) and gpu:
+            raise ValueError(NO_WEIGHTED_KERNEL)
         if loss not in LOSSES:
             raise ValueError("multi-model: the loss must be logistic, least squares or squared hinge "
                              "(softmax has its own plan)")
@@ -53,6 +59,8 @@ class MultiModelGradPlan(BlockGradPlan):
                  partitions: Dict[int, Tuple[torch.Tensor, torch.Tensor]], prec: Precision, loss: int, models: int,
                  d: int):
         self.check_supported(prec, int(loss), models)
+        if is_weighted(int(loss)) and any(X.is_cuda for X, _ in partitions.values()):
+            raise ValueError(NO_WEIGHTED_KERNEL)
         self.loss = int(loss)
         self.models = int(models)
         super().__init__(messages, partitions, prec, models, d)

@@ -135,7 +135,7 @@ def scale_cases(out):
 
 
 def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_000), precs=("fp64", "fp32"),
-                losses=("logistic",), classes=(2,), models=(2,), layouts_only=None):
+                losses=("logistic",), classes=(2,), models=(2,), layouts_only=None, weighted=False):
     """Shape sweep of the dense gradient against the device-copy ceiling (round-2 verdict item 6).
 
     For every (precision, d, n): n rows in 8 partitions, two message layouts -- ``naive`` (one
@@ -148,10 +148,13 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
     (rows of at most 1024 columns, fp64 / fp32; other precisions are skipped with a note).  ``multimodel`` runs
     MultiModelGradPlan (logistic) on the same X and labels, once per M of ``models``; ``ms_per_model`` is its time
     over M, to hold against the one-model logistic rows.
+    ``weighted``: the same plans run the weighted code of the loss (logistic, squared_hinge) on labels
+    y~ = y * w, w = 10**U(-2, 2) drawn once per partition -- the A/B of class / sample weights against a run without
+    the flag.
     """
     import torch
 
-    from erasurehead_amd.models.losses import LOSS_NAMES
+    from erasurehead_amd.models.losses import LOSS_NAMES, weighted_kind
     from erasurehead_amd.ops import DenseGradPlan, SoftmaxGradPlan, get_precision
     from erasurehead_amd.ops.multimodel import MultiModelGradPlan
 
@@ -167,6 +170,8 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
                 for p in range(8):
                     X = torch.empty(rpp, prec.ld(d), device="cuda", dtype=prec.storage).uniform_(-1, 1)
                     y = torch.where(torch.rand(rpp, device="cuda") > 0.5, 1.0, -1.0).to(prec.acc)
+                    if weighted:
+                        y = y * (10.0 ** torch.empty(rpp, device="cuda", dtype=torch.float64).uniform_(-2, 2)).to(prec.acc)
                     parts[p] = (X, y)
                 nbytes = parts[0][0].numel() * parts[0][0].element_size()
                 dst = torch.empty_like(parts[0][0])
@@ -213,12 +218,14 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
                                 print(json.dumps(r), flush=True)
                                 del plan, G, sm
                             continue
-                        plan = DenseGradPlan([[(p, 1.0) for p in m] for m in msgs], parts, prec, LOSS_NAMES[loss], d)
+                        kind = weighted_kind(LOSS_NAMES[loss]) if weighted else LOSS_NAMES[loss]
+                        plan = DenseGradPlan([[(p, 1.0) for p in m] for m in msgs], parts, prec, kind, d)
                         G = plan.out_buffer()[0]
                         ms = _time(lambda: plan.run(beta, G), reps=20)
                         distinct = 8 * nbytes / 1e12  # TB
                         r = {"kernel": "grad_dense_sweep", "precision": prec_name, "d": d, "n": n, "layout": lay,
-                             "loss": loss, "choice": plan.choice.label() if plan.choice else "twopass", "ms": ms,
+                             "loss": loss, "weighted": weighted,
+                             "choice": plan.choice.label() if plan.choice else "twopass", "ms": ms,
                              "distinct_TBps": distinct / ms * 1e3, "copy_TBps": ceiling,
                              "frac": distinct / ms * 1e3 / ceiling}
                         out.append(r)
@@ -313,19 +320,25 @@ UNITS_PROBE = False  # --units-probe
 
 
 def sparse_cases(out, names=("covtype", "kc_house_data", "amazon-dataset"), ell_only=False, layouts_only=None,
-                 rows="both"):
+                 rows="both", weighted=False):
+    """``weighted``: the weighted logistic code on labels y~ = y * w, w = 10**U(-2, 2)."""
+    import numpy as np
     import torch
 
     from erasurehead_amd.data.synthetic import REAL_SHAPES, onehot_partitions
-    from erasurehead_amd.models.losses import LOGISTIC
+    from erasurehead_amd.models.losses import LOGISTIC, LOGISTIC_W
     from erasurehead_amd.ops import SparseGradPlan, get_precision
 
     prec = get_precision("fp64")
+    kind = LOGISTIC_W if weighted else LOGISTIC
     for name in names:
         n, d, f = REAL_SHAPES[name]
         W = 8
         parts_l, _, dd = onehot_partitions(n, d, f, W, seed=1)
         parts = {p: xy for p, xy in enumerate(parts_l)}
+        if weighted:
+            wrng = np.random.RandomState(2)
+            parts = {p: (X, y * 10.0 ** wrng.uniform(-2, 2, len(y))) for p, (X, y) in parts.items()}
         layouts = {"naive": [[(w, 1.0)] for w in range(W)],
                    "s1_replicas": [[(w, 1.0), ((w + 1) % W, 1.0)] for w in range(W)],  # 8 workers, 2 partitions each
                    # FRC / AGC s = 1: groups {2g, 2g + 1} send the sum of both partitions (merged units when small)
@@ -334,7 +347,7 @@ def sparse_cases(out, names=("covtype", "kc_house_data", "amazon-dataset"), ell_
             layouts = {k: v for k, v in layouts.items() if k in layouts_only}
         ells = (True,) if ell_only else ("auto",) if rows == "auto" else (True, False)
         for (layout, msgs), use_ell in [(x, e) for x in layouts.items() for e in ells]:
-            plan = SparseGradPlan(msgs, parts, prec, LOGISTIC, dd, device="cuda", use_ell=use_ell)
+            plan = SparseGradPlan(msgs, parts, prec, kind, dd, device="cuda", use_ell=use_ell)
             beta = torch.randn(prec.ld(dd), device="cuda", dtype=torch.float64) * 0.1
             G = plan.out_buffer()[0]
             if UNITS_PROBE and plan.dst is not None:  # timing probe, not a gradient: each unit's first row only
@@ -342,6 +355,7 @@ def sparse_cases(out, names=("covtype", "kc_house_data", "amazon-dataset"), ell_
             ms = _time(lambda: plan.run(beta, G))
             kern = ("ell16" if plan.idx16 else "ell32") if plan.ell else "csr"
             r = {"kernel": f"grad_sparse ({kern} rows, CSC{16 if plan.row16 else 32} tiles)", "layout": layout,
+                 "weighted": weighted,
                  "units": len(plan.units) if plan.units else None, "identity": bool(plan.identity),
                  "dataset_shape": name, "rows_distinct": plan.nrows, "rows_in_messages": plan.msg_rows,
                  "nnz": int(plan.nnz), "d": dd, "ms": ms, "nnz_per_us": plan.nnz / (ms * 1e3),
@@ -367,6 +381,9 @@ def main():
                          "softmax, multimodel = the M-model logistic kernel of an (alpha, lr) sweep)")
     ap.add_argument("--classes", default="2", help="--only sweep --loss softmax: class counts, e.g. 2,4,7,8")
     ap.add_argument("--models", default="2", help="--only sweep --loss multimodel: model counts, e.g. 2,4,8")
+    ap.add_argument("--weighted", action="store_true",
+                    help="--only sweep / sparse: the weighted code of the loss on labels y * w, w = 10**U(-2, 2) (logistic, "
+                         "squared_hinge; sparse: logistic) -- compare with a run without the flag")
     ap.add_argument("--sweep-layouts", default=None, help="--only sweep: naive,agc (default: both)")
     ap.add_argument("--sparse-shapes", default="covtype,kc_house_data,amazon-dataset", help="--only sparse: datasets")
     ap.add_argument("--ell-only", action="store_true", help="--only sparse: skip the CSR row pass")
@@ -397,6 +414,8 @@ def main():
     losses = tuple(a.loss.split(","))
     if any(x not in LOSS_CHOICES and x != "multimodel" for x in losses):
         ap.error(f"--loss: names from {sorted(LOSS_CHOICES) + ['multimodel']}")
+    if a.weighted and any(x in ("least_squares", "softmax", "multimodel") for x in losses):
+        ap.error("--weighted: logistic or squared_hinge (no other kernel has a weighted instance)")
     out = []
     if a.only in (None, "dense"):
         dense_cases(out)
@@ -408,7 +427,7 @@ def main():
         sweep_cases(out, ds=tuple(int(x) for x in a.ds.split(",")), ns=tuple(int(float(x)) for x in a.ns.split(",")),
                     precs=tuple(a.precs.split(",")), losses=losses, classes=tuple(int(c) for c in a.classes.split(",")),
                     models=tuple(int(m) for m in a.models.split(",")),
-                    layouts_only=a.sweep_layouts.split(",") if a.sweep_layouts else None)
+                    layouts_only=a.sweep_layouts.split(",") if a.sweep_layouts else None, weighted=a.weighted)
     if a.only == "choices":
         if a.shapes:
             choice_cases(out, [(p, int(d), int(float(n))) for p, d, n in (x.split(":") for x in a.shapes.split(","))],
@@ -417,7 +436,8 @@ def main():
             choice_cases(out, layout=a.layout)
     if a.only in (None, "sparse"):
         sparse_cases(out, names=tuple(a.sparse_shapes.split(",")), ell_only=a.ell_only,
-                     layouts_only=a.sparse_layouts.split(",") if a.sparse_layouts else None, rows=a.sparse_rows)
+                     layouts_only=a.sparse_layouts.split(",") if a.sparse_layouts else None, rows=a.sparse_rows,
+                     weighted=a.weighted)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         for r in out:

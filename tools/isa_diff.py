@@ -66,6 +66,8 @@ def functions(co: str):
             line = line.split("//")[0].strip()
             if not line or re.fullmatch(r"<[^>]+>:", line):  # blank, or a branch-target label
                 continue
+            if line == "...":  # zero padding up to the next symbol: the last symbol of a code object has none
+                continue
             body.append(re.sub(r"\s+", " ", line))
         funcs[m.group(1)] = body
     return funcs
