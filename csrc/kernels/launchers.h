@@ -152,7 +152,8 @@ constexpr int kSparseMaxDst = 4;
 hipError_t grad_sparse_launch(int dtype, int loss, const SparseArgs& a, const void* beta, hipStream_t st,
                               const int* gate = nullptr);
 
-// ---- blocked models: multi-class softmax and several scalar-loss models (grad_softmax.hip, grad_multimodel.hip) ----
+// ---- blocked models: multi-class softmax, several scalar-loss models and one-vs-rest (grad_softmax.hip,
+// grad_multimodel.hip, grad_ovr.hip) ----
 // One contract for both (grad_blocks.h).  The model beta and every Gb row are [blocks][ld_x] (D = blocks * ld_x
 // elements), Gb[p] = gradient of partition p's loss sum with coefficient 1, for every distinct local partition in
 // one pass over X.  segs / tasks: the dense task table (grad_dense.h Segment / Task; Task::slot = partition row of
@@ -175,6 +176,12 @@ hipError_t grad_softmax_launch(int dtype, int classes, const void* segs, const v
 hipError_t grad_models_launch(int dtype, int loss, int models, const void* segs, const void* tasks, int ntasks,
                               const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb, int d_x,
                               int ld_x, hipStream_t st, const int* gate = nullptr);
+// One-vs-rest (grad_ovr.hip): `classes` binary models of one scalar loss, labels are class indices held as floats and
+// Gb[p] block k = gradient at beta block k for the labels (y == k ? +1 : -1).  dtype as for grad_models_launch;
+// loss kLogistic or kSquaredHinge only.
+hipError_t grad_ovr_launch(int dtype, int loss, int classes, const void* segs, const void* tasks, int ntasks,
+                           const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb, int d_x,
+                           int ld_x, hipStream_t st, const int* gate = nullptr);
 
 // layout probes of the bf16 MFMA gradient (grad_mfma.hip): one 16x16x32 product; one transposing read
 hipError_t mfma_probe_launch(const float* A, const float* B, float* C, hipStream_t st);

@@ -34,6 +34,10 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--loss", default="auto", choices=["auto", *LOSS_CHOICES])
     g.add_argument("--classes", type=int, default=None,
                    help="--loss softmax: number of classes, 2..8 (default 2); labels are class indices 0..C-1")
+    g.add_argument("--ovr", type=int, default=None, metavar="C",
+                   help="--loss logistic | squared_hinge: one-vs-rest over C classes, 2..8: C binary models (class k "
+                        "against the rest) from one pass over X per round; labels are class indices 0..C-1, "
+                        "prediction is the largest score")
     g.add_argument("--num-itrs", type=int, default=100)
     g.add_argument("--lr", type=float, default=10.0)
     g.add_argument("--lr-schedule", default="const", choices=["const", "invscaling", "exponential"],
@@ -150,7 +154,7 @@ def parse(argv: List[str]):
                     integrity=not a.no_integrity, delay_on=a.delay_on, slow_ranks=parse_slow_ranks(a.slow_ranks),
                     dedicated_master=a.dedicated_master, device_records=a.device_records,
                     sweep_alpha=a.alphas, sweep_lr=a.lrs, l1=a.l1, sweep_l1=a.l1s,
-                    class_weight=a.class_weight, sample_weights=a.sample_weights)
+                    class_weight=a.class_weight, sample_weights=a.sample_weights, ovr=a.ovr)
     return cfg, a
 
 

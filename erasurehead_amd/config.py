@@ -18,6 +18,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 SWEEP_MIN_MODELS, SWEEP_MAX_MODELS = 2, 8  # csrc/kernels/launchers.h kMinBlocks / kMaxBlocks
+OVR_MIN_CLASSES, OVR_MAX_CLASSES = 2, 8  # likewise: the classes of a one-vs-rest run are the blocks
 
 
 def parse_class_weight(spec):
@@ -63,6 +64,9 @@ class RunConfig:
     precision: str = "fp64"  # fp64 | fp32 | bf16 | fp32x64 worker compute (master state always fp64)
     loss: str = "auto"  # auto (reference dispatch) | logistic | least_squares | squared_hinge | softmax
     classes: Optional[int] = None  # softmax only: number of classes, 2..8 (default 2)
+    # one-vs-rest over C = 2..8 classes with the logistic or the squared-hinge loss (auto: logistic): C binary models,
+    # class k against the rest, trained from one pass over X per round (ops/ovr.py); labels are class indices
+    ovr: Optional[int] = None
     # (alpha, lr) sweep: M = 2..8 models trained in one run from one pass over X per round (ops/multimodel.py).
     # The lists are zipped; an absent list or one of length 1 is broadcast (absent: the run's alpha / lr).
     sweep_alpha: Optional[List[float]] = None
@@ -149,6 +153,8 @@ class RunConfig:
             raise ValueError("delay_on must be collector or worker")
         if self.drain not in (None, "all", "carry", "lazy"):
             raise ValueError("drain must be all, carry or lazy")
+        if self.ovr is not None:
+            self._check_ovr()
         if self.loss == "softmax":
             self.classes = 2 if self.classes is None else int(self.classes)
             if not 2 <= self.classes <= 8:
@@ -167,6 +173,23 @@ class RunConfig:
                              f"cannot carry the weight there); logistic or squared_hinge")
         if self.sample_weights is not None and self.data == "synthetic":
             raise ValueError("--sample-weights: not with --data synthetic (there is no label.dat the file could match)")
+
+    def _check_ovr(self) -> None:
+        """The limits of a one-vs-rest run that the configuration alone decides, each a ValueError naming --ovr."""
+        self.ovr = int(self.ovr)
+        if not OVR_MIN_CLASSES <= self.ovr <= OVR_MAX_CLASSES:
+            raise ValueError(f"--ovr: classes must be in {OVR_MIN_CLASSES}..{OVR_MAX_CLASSES}, got {self.ovr}")
+        if self.loss in ("least_squares", "softmax"):
+            raise ValueError(f"--ovr: not supported with --loss {self.loss} (one-vs-rest trains binary classifiers: "
+                             f"logistic or squared_hinge; auto means logistic)")
+        if self.classes is not None:
+            raise ValueError("--ovr: cannot be combined with --classes (a softmax option); --ovr C gives the classes")
+        if self.sweep_alpha is not None or self.sweep_lr is not None or self.sweep_l1 is not None:
+            raise ValueError("--ovr: cannot be combined with a sweep (--alphas / --lrs / --l1s): the class blocks "
+                             "share one (alpha, lr, l1)")
+        if self.class_weight is not None or self.sample_weights is not None:
+            raise ValueError("--ovr: --class-weight / --sample-weights are not supported (the labels are class "
+                             "indices and cannot carry a weight)")
 
     def _sweep_lists(self) -> Optional[Tuple[List[float], List[float], List[float]]]:
         """([alpha_k], [lr_k], [l1_k]) of a sweep run, every list broadcast to the M models; None without a list."""

@@ -13,6 +13,10 @@ result names carry the prefix ``sweep{k}_`` (before ``sqhinge_`` where that appl
 Softmax runs are scored by cross-entropy and accuracy: the console line carries the accuracy where the
 logistic line has the AUC, ``EvalResult.auc`` (and the ``auc`` result file) hold the accuracy, and the
 result names carry the prefix ``softmax_``.
+One-vs-rest runs (--ovr C) are scored like softmax runs with their own loss: training and test loss are the mean over
+rows of sum_k l(y_k z_k) (l the run's binary loss, y_k = +1 for the row's class and -1 for the others), the accuracy
+(argmax_k z_k, first on ties) stands where softmax puts it, and the result names carry the prefix ``ovr_`` (before
+``sqhinge_`` where that applies).
 Runs with an L1 penalty (--l1 / --l1s, some lambda > 0) also report sparsity: ``EvalResult.nnz`` (the non-zero
 data columns of every iterate) and ``l1_penalty`` are filled for every run; with some lambda > 0 the console gets
 one line ``>> L1: l1 = ..., nnz = k of d`` per model, the ``>> Model k:`` line of a sweep names ``l1``, and an
@@ -31,7 +35,7 @@ import numpy as np
 import torch
 
 from ..data import io as dio
-from ..models.losses import SQUARED_HINGE, base_kind, is_classification, is_multiclass
+from ..models.losses import LOGISTIC, SQUARED_HINGE, base_kind, is_classification, is_multiclass
 from ..ops.eval import auc_columns, loss_sums, predictions, predictions_and_loss, sign_labels
 from ..utils import report
 from .trainer import TrainResult, Trainer
@@ -39,6 +43,7 @@ from .trainer import TrainResult, Trainer
 
 SQHINGE_PREFIX = "sqhinge_"  # result files of squared-hinge runs (next to the logistic names)
 SOFTMAX_PREFIX = "softmax_"
+OVR_PREFIX = "ovr_"  # result files of one-vs-rest runs (before sqhinge_)
 WEIGHTED_PREFIX = "weighted_"  # result files of runs with class / sample weights
 SOFTMAX_P_ELEMS = 1 << 26  # logits held at once by the softmax evaluation (rounds are chunked to fit)
 
@@ -52,20 +57,21 @@ class EvalResult:
     n_test: int
     files: Optional[Dict[str, str]] = None  # sweep runs: {"sweep{k}_" + key: path} of every model
     best: Optional[int] = None  # sweep runs (arrays [R, M]): the model with the lowest final test loss
-    nnz: Optional[np.ndarray] = None  # non-zero data columns of every iterate: [R], sweep [R, M]; softmax: all C blocks
+    # non-zero data columns of every iterate: [R], sweep [R, M]; softmax and one-vs-rest: all C blocks
+    nnz: Optional[np.ndarray] = None
     l1_penalty: Optional[np.ndarray] = None  # l1 * ||beta||_1 of every iterate, shaped like nnz
 
 
 def sparsity(trainer: Trainer, betaset: np.ndarray):
     """(nnz, l1_penalty) of every iterate over the data columns: [R], or [R, M] for a sweep run (softmax counts
-    over its C class blocks: they are one model with one lambda)."""
+    and one-vs-rest count over their C class blocks: they are one model with one lambda)."""
     B = np.asarray(betaset, dtype=np.float64)
     R, M = B.shape[0], getattr(trainer, "models", 1)
     if M > 1:
         blocks = B.reshape(R, M, trainer.ld_x)[:, :, : trainer.d_x]
         l1 = np.asarray(trainer.sweep_l1, dtype=np.float64)
         return np.count_nonzero(blocks, axis=2), np.abs(blocks).sum(axis=2) * l1
-    if is_multiclass(trainer.loss):
+    if is_multiclass(trainer.loss) or getattr(trainer, "ovr", False):
         B = B.reshape(R, trainer.classes, trainer.ld_x)[:, :, : trainer.d_x].reshape(R, -1)
     else:
         B = B[:, : trainer.d]
@@ -141,21 +147,55 @@ def _softmax_sums(X, y, B, classes: int, d_x: int):
     return ce.numpy(), hit.numpy()
 
 
+def _ovr_sums(X, y, B, classes: int, d_x: int, kind: int):
+    """(loss sums [R], correct counts [R]) of the rows X, y (class indices) for the one-vs-rest models
+    B [R * classes, ld_x]: sum over rows and classes of l(y_k z_k) with l the logistic or the squared-hinge loss;
+    scores from the prediction GEMM, rounds chunked like _softmax_sums."""
+    n, R = X.shape[0], B.shape[0] // classes
+    tot = torch.zeros(R, dtype=torch.float64)
+    hit = torch.zeros(R, dtype=torch.float64)
+    step = max(1, SOFTMAX_P_ELEMS // max(1, n * classes))
+    yl = y.to(X.device).long()
+    own = yl[:, None, None] == torch.arange(classes, device=X.device)[None, None, :]
+    for r0 in range(0, R, step):
+        r1 = min(R, r0 + step)
+        Z = predictions(X, B[r0 * classes: r1 * classes], d_x).double().reshape(n, r1 - r0, classes)
+        m = torch.where(own, -Z, Z)  # -y_k z_k
+        if kind == LOGISTIC:
+            v = torch.clamp(m, min=0) + torch.log1p(torch.exp(-m.abs()))
+        else:
+            v = torch.clamp(1.0 + m, min=0) ** 2
+        tot[r0:r1] = v.sum(dim=(0, 2)).cpu()
+        hit[r0:r1] = (Z.argmax(dim=2) == yl[:, None]).double().sum(0).cpu()
+    return tot.numpy(), hit.numpy()
+
+
 def _evaluate_softmax(trainer: Trainer, res: TrainResult, log, write: bool) -> EvalResult:
+    """Softmax and one-vs-rest runs: a [classes][ld_x] model scored by its loss and the test accuracy."""
     cfg, dev, prec = trainer.cfg, trainer.env.device, trainer.prec
     C, d_x, ld_x = trainer.classes, trainer.d_x, trainer.ld_x
     R = res.betaset.shape[0]
     B = torch.from_numpy(np.ascontiguousarray(res.betaset)).to(dev).reshape(R * C, ld_x)
     parts = eval_partitions(trainer)
+    if getattr(trainer, "ovr", False):
+        kind = trainer.loss
+
+        def sums(X, y):
+            return _ovr_sums(X, y, B, C, d_x, kind)
+        prefix = OVR_PREFIX + (SQHINGE_PREFIX if kind == SQUARED_HINGE else "")
+    else:
+        def sums(X, y):
+            return _softmax_sums(X, y, B, C, d_x)
+        prefix = SOFTMAX_PREFIX
     if cfg.verbose:
         log(report.total_time_line(res.total_time))
     tr_sum, n_train = np.zeros(R), 0
     for X, y in _train_chunks(trainer, parts, prec, dev):
-        s, _ = _softmax_sums(X, y, B, C, d_x)
+        s, _ = sums(X, y)
         tr_sum += s
         n_train += X.shape[0]
     Xt, yt = trainer.source.test(prec, dev)
-    te_sum, hits = _softmax_sums(Xt, yt, B, C, d_x)
+    te_sum, hits = sums(Xt, yt)
     n_test = Xt.shape[0]
     training_loss = tr_sum / max(1, n_train)
     testing_loss = te_sum / max(1, n_test)
@@ -168,7 +208,7 @@ def _evaluate_softmax(trainer: Trainer, res: TrainResult, log, write: bool) -> E
             log(_nnz_line(cfg.l1, nnz[-1], C * d_x))
     files = None
     if write:
-        names = {k: SOFTMAX_PREFIX + v for k, v in trainer.scheme.output_names(cfg.fix_quirks).items()}
+        names = {k: prefix + v for k, v in trainer.scheme.output_names(cfg.fix_quirks).items()}
         data_dir = getattr(trainer.source, "data_dir", None) or cfg.input_dir
         files = report.write_results(dio.results_dir(data_dir), names, training_loss, testing_loss, acc,
                                      res.timeset, res.worker_timeset, cfg.full_precision_outputs)
@@ -242,7 +282,7 @@ def _evaluate_sweep(trainer: Trainer, res: TrainResult, log, write: bool) -> Eva
 
 def evaluate(trainer: Trainer, res: TrainResult, log=None, write: bool = True) -> EvalResult:
     log = log or report.log
-    if is_multiclass(trainer.loss):
+    if is_multiclass(trainer.loss) or getattr(trainer, "ovr", False):
         return _evaluate_softmax(trainer, res, log, write)
     if getattr(trainer, "models", 1) > 1:
         return _evaluate_sweep(trainer, res, log, write)

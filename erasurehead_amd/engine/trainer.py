@@ -56,6 +56,7 @@ from ..models.losses import (LEAST_SQUARES, LOGISTIC, LOSS_CHOICES, SOFTMAX, SQU
 from ..ops.grad import DenseGradPlan, SharedGradPlan, SparseGradPlan
 from ..ops.softmax import SoftmaxGradPlan
 from ..ops.multimodel import MultiModelGradPlan
+from ..ops.ovr import OvrGradPlan
 from ..ops.precision import get_precision
 from ..ops.update import combine_update, combine_update_blocks, combine_update_prox
 from ..parallel.collector import ArrivalCollector
@@ -137,7 +138,8 @@ class Trainer:
     def _start_eval_warmup(self):
         """Master on a GPU, classification runs (logistic, squared hinge) that will be evaluated: load the AUC path's code objects on a
         side thread while the data is generated / loaded (ops/eval.warm_auc; 0.6 s cold)."""
-        if not (self.env.is_master and self.env.gpu and self.cfg.evaluate and is_classification(self.loss)):
+        if not (self.env.is_master and self.env.gpu and self.cfg.evaluate and is_classification(self.loss)) \
+                or self.ovr:  # a one-vs-rest run is scored by accuracy, not by AUC
             return None
         import threading
 
@@ -189,6 +191,18 @@ class Trainer:
             self.loss = weighted_kind(self.loss)
         # multi-class softmax: the model is [classes][ld_x] flattened (ops/softmax.py); 1 for every other loss
         self.classes = check_classes(cfg.classes or 2) if self.loss == SOFTMAX else 1
+        # one-vs-rest (--ovr C): C binary models of the scalar loss in the same [classes][ld_x] layout (ops/ovr.py);
+        # self.loss stays the binary loss.  blocked: the model is class-major blocks, as softmax's is
+        self.ovr = cfg.ovr is not None
+        if self.ovr:
+            if self.loss == LEAST_SQUARES:
+                raise ValueError("--ovr: --loss auto resolves to least squares for this run, which has no "
+                                 "one-vs-rest form; name --loss logistic or squared_hinge")
+            if self.weighted:  # (a source that brings sample weights of its own; the flags are the config's to reject)
+                raise ValueError("--ovr: class / sample weights are not supported (the labels are class indices and "
+                                 "cannot carry a weight)")
+            self.classes = check_classes(cfg.ovr)
+        self.blocked = self.loss == SOFTMAX or self.ovr
         # (alpha, lr) sweep: M models of one scalar loss, the model [M][ld_x] flattened (ops/multimodel.py)
         sweep = cfg.sweep()
         self.models = len(sweep) if sweep else 1
@@ -256,7 +270,7 @@ class Trainer:
         if source is None:
             if cfg.data == "synthetic":
                 source = SyntheticSource(cfg.n_rows, cfg.n_cols, sch.n_partition_files, cfg.data_seed,
-                                         classes=self.classes if self.loss == SOFTMAX else None)
+                                         classes=self.classes if self.blocked else None)
             else:
                 data_dir = dio.dataset_dir(cfg.input_dir, cfg.is_real, cfg.dataset, cfg.n_rows, cfg.n_cols)
                 data_dir = data_dir + sch.data_subdir()
@@ -266,13 +280,17 @@ class Trainer:
             source = self._weighted_source(source)
         self.source = source
         # d_x / ld_x: the data's columns and row stride; d / ld: everything model-sized (beta, messages,
-        # history).  They differ only for softmax, whose model is the flattened [classes][ld_x].
+        # history).  They differ only for softmax and one-vs-rest, whose model is the flattened [classes][ld_x].
         self.d_x = cfg.n_cols
         self.ld_x = self.prec.ld(self.d_x)
         self.d, self.ld = self.d_x, self.ld_x
         if self.loss == SOFTMAX:
             self.d = self.ld = self.classes * self.ld_x
             SoftmaxGradPlan.check_supported(self.prec, self.classes, source.is_sparse)  # before any load
+        if self.ovr:
+            self.d = self.ld = self.classes * self.ld_x
+            OvrGradPlan.check_supported(self.prec, self.loss, self.classes, source.is_sparse, self.ld_x,
+                                        bool(self.env.gpu))  # before any load
         if self.models > 1:
             self.d = self.ld = self.models * self.ld_x
             MultiModelGradPlan.check_supported(self.prec, self.loss, self.models, source.is_sparse, self.ld_x,
@@ -291,6 +309,8 @@ class Trainer:
         def make_plan(messages):
             if self.loss == SOFTMAX:  # shares the distinct partitions by itself: --share-partitions changes nothing
                 return SoftmaxGradPlan(messages, parts, self.prec, self.classes, self.d_x)
+            if self.ovr:  # likewise
+                return OvrGradPlan(messages, parts, self.prec, self.loss, self.classes, self.d_x)
             if self.models > 1:  # likewise: every distinct partition once, whatever --share-partitions says
                 return MultiModelGradPlan(messages, parts, self.prec, self.loss, self.models, self.d_x)
             if source.is_sparse:
@@ -300,7 +320,7 @@ class Trainer:
                 kw["pack"] = False
             return DenseGradPlan(messages, parts, self.prec, self.loss, self.d, **kw)
 
-        share = cfg.share_partitions and self.loss != SOFTMAX and self.models == 1
+        share = cfg.share_partitions and not self.blocked and self.models == 1
         if share and SharedGradPlan.worthwhile(segs, lambda p: parts[p][0].shape[0]):
             self.plan = SharedGradPlan(segs, make_plan)
         else:
@@ -454,7 +474,7 @@ class Trainer:
         counts = collections.Counter(p for m in self.local_msgs for p, _ in m.segments)
         if not counts or max(counts.values()) < 2:
             return "none"
-        if isinstance(plan, (SharedGradPlan, SparseGradPlan, SoftmaxGradPlan, MultiModelGradPlan)):
+        if isinstance(plan, (SharedGradPlan, SparseGradPlan, SoftmaxGradPlan, MultiModelGradPlan, OvrGradPlan)):
             return "encoded"
         return "separate"
 
@@ -462,14 +482,14 @@ class Trainer:
     def _init_beta(self):
         """beta_0: randn (naive/replication/approx) or zeros (ref §2.2 'Per-scheme beta init')."""
         d = self.d
-        nb = self.classes * self.d_x  # softmax: classes * d_x values, scattered into [classes][:d_x] below
+        nb = self.classes * self.d_x  # softmax, one-vs-rest: classes * d_x values, scattered into [classes][:d_x] below
         if self.scheme.init_zero:
             b0 = np.zeros(nb)
         elif self.cfg.seed is not None:
             b0 = np.random.RandomState(self.cfg.seed + 1).randn(nb)
         else:
             b0 = np.random.randn(nb)
-        if self.loss == SOFTMAX:  # the padding columns of every class block stay zero
+        if self.blocked:  # the padding columns of every class block stay zero
             full = np.zeros((self.classes, self.ld_x))
             full[:, : self.d_x] = b0.reshape(self.classes, self.d_x)
             b0 = full.ravel()
@@ -865,6 +885,8 @@ class Trainer:
                                   "partitions": len({p for m in self.local_msgs for p, _ in m.segments})}
         if self.models > 1:
             rep.update(models=self.models, sweep_alpha=list(self.sweep_alpha), sweep_lr=list(self.sweep_lr))
+        if self.ovr:
+            rep.update(ovr=True, classes=self.classes)
         rep.update(l1=list(self.sweep_l1) if self.models > 1 else float(self.cfg.l1), prox=bool(self.prox))
         rep.update(weighted=bool(self.weighted), class_weight=list(self.class_weight) if self.weighted else None,
                    weight_sum_over_n=self.weight_sum_over_n)
@@ -1343,6 +1365,11 @@ class Trainer:
             if have_l1s != [float(x) for x in self.sweep_l1]:
                 raise ValueError(f"checkpoint {path} was written by a run with sweep_l1 = {have_l1s}; this run has "
                                  f"sweep_l1 = {list(self.sweep_l1)}")
+        # one-vs-rest likewise; a checkpoint without the key was written by a run without --ovr
+        have_ovr = st.get("ovr")
+        if have_ovr != self.cfg.ovr:
+            raise ValueError(f"checkpoint {path} was written by a run with ovr = {have_ovr}; this run has "
+                             f"ovr = {self.cfg.ovr} (--ovr)")
         # class / sample weights likewise; a checkpoint without the key was written by an unweighted run
         have_w = st.get("weights")
         if have_w != self.weight_spec:
@@ -1377,6 +1404,8 @@ class Trainer:
         state["l1"] = float(self.cfg.l1)
         if self.weighted:
             state["weights"] = self.weight_spec
+        if self.ovr:
+            state["ovr"] = int(self.cfg.ovr)
         if getattr(self.scheme, "B", None) is not None:
             state["B"] = torch.from_numpy(np.ascontiguousarray(self.scheme.B, dtype=np.float64))
         tmp = path + ".tmp"

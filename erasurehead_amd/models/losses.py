@@ -22,6 +22,12 @@ B [C, d] and travels flattened class-major (on the device [C][ld_x], padding col
                              B_0 = 0, B_1 = beta gives G_1 = logistic_grad(X, 2y - 1, beta), G_0 = -G_1)
   cross-entropy              CE = logsumexp(z) - z_y  (never -log p_y)
   step size                  the CE Hessian is bounded by XtX / 2 (logistic: XtX / 4): lr 5 where logistic uses 10
+
+One-vs-rest (not in the reference): the same labels and [C, d] layout, C binary models of the logistic or the
+squared-hinge loss, model k with the labels y_k = +1 where y = k and -1 elsewhere:
+  objective                  (1/n) sum_rows sum_k l(y_k * x . B_k)
+  worker gradient            G_k = the scalar-loss gradient at (B_k, y_k)
+  prediction                 argmax_k x . B_k (first on ties)
 """
 from __future__ import annotations
 
@@ -184,6 +190,40 @@ def softmax_pack(B: np.ndarray, ld_x: int) -> np.ndarray:
     out = np.zeros((B.shape[0], ld_x))
     out[:, : B.shape[1]] = B
     return out.ravel()
+
+
+def ovr_labels(y: np.ndarray, classes: int) -> np.ndarray:
+    """[n, C] of +-1: column k is +1 where the class index y is k, -1 elsewhere (the labels model k of a
+    one-vs-rest run sees)."""
+    y = np.asarray(y)
+    return np.where(y[:, None] == np.arange(int(classes))[None, :], 1.0, -1.0)
+
+
+def ovr_grad(kind: int, X, y: np.ndarray, B: np.ndarray, coef=None) -> np.ndarray:
+    """[C, d]: block k is the scalar-loss gradient (logistic or squared hinge) at (B_k, ovr_labels(y)[:, k])."""
+    if kind not in (LOGISTIC, SQUARED_HINGE):
+        raise ValueError(f"one-vs-rest: loss kind {kind} is not logistic or squared hinge")
+    B = np.asarray(B, dtype=np.float64)
+    Y = ovr_labels(y, B.shape[0])
+    return np.stack([_GRADS[kind](X, Y[:, k], B[k], coef) for k in range(B.shape[0])])
+
+
+def ovr_row_loss(kind: int, y: np.ndarray, Z: np.ndarray) -> np.ndarray:
+    """Per-row one-vs-rest loss sum_k l(y_k z_k) from scores Z [n, C]."""
+    if kind not in (LOGISTIC, SQUARED_HINGE):
+        raise ValueError(f"one-vs-rest: loss kind {kind} is not logistic or squared hinge")
+    Z = np.asarray(Z, dtype=np.float64)
+    m = -ovr_labels(y, Z.shape[1]) * Z
+    if kind == LOGISTIC:
+        v = np.maximum(m, 0.0) + np.log1p(np.exp(-np.abs(m)))
+    else:
+        v = np.maximum(0.0, 1.0 + m) ** 2
+    return v.sum(axis=1)
+
+
+def ovr_loss(kind: int, y: np.ndarray, Z: np.ndarray, n: Optional[int] = None) -> float:
+    """(1/n) sum_rows sum_k l(y_k z_k) over scores Z [n, C]."""
+    return float(ovr_row_loss(kind, y, Z).sum() / (len(y) if n is None else n))
 
 
 def sweep_unpack(betaset: np.ndarray, models: int, d_x: int) -> np.ndarray:

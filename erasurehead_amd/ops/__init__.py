@@ -3,5 +3,6 @@ from .eval import auc_columns, loss_sums, predictions
 from .grad import DenseGradPlan, SparseGradPlan, choose_cpl
 from .softmax import SoftmaxGradPlan
 from .multimodel import MultiModelGradPlan
+from .ovr import OvrGradPlan
 from .precision import PRECISIONS, Precision, get_precision
 from .update import combine_update, combine_update_blocks, combine_update_prox

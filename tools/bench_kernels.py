@@ -8,7 +8,8 @@
   device-copy ceiling, distinct-row and replica-bundle layouts; ``--loss a,b,...`` times each named
   loss on the same data in the same process, in the order given (repeat names to alternate);
   ``softmax`` among them times the one-pass multi-class kernel for every ``--classes C,...`` and
-  ``multimodel`` the one-pass M-model kernel of an (alpha, lr) sweep for every ``--models M,...``;
+  ``multimodel`` the one-pass M-model kernel of an (alpha, lr) sweep for every ``--models M,...`` and ``ovr``
+  the one-pass one-vs-rest kernel (logistic) for every ``--classes C,...``;
 * sparse one-hot gradients on covtype / kc_house / amazon-shaped data (the reference's real
   datasets, synthetic stand-ins of the same shape): the ELL path against the generic
   sorted-COO path.
@@ -147,7 +148,8 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
     ``softmax`` runs SoftmaxGradPlan on the same X with labels randint(0, C), once per C of ``classes``
     (rows of at most 1024 columns, fp64 / fp32; other precisions are skipped with a note).  ``multimodel`` runs
     MultiModelGradPlan (logistic) on the same X and labels, once per M of ``models``; ``ms_per_model`` is its time
-    over M, to hold against the one-model logistic rows.
+    over M, to hold against the one-model logistic rows.  ``ovr`` runs OvrGradPlan (logistic) on the same X with labels
+    randint(0, C), once per C of ``classes``; ``ms_per_model`` is its time over C.
     ``weighted``: the same plans run the weighted code of the loss (logistic, squared_hinge) on labels
     y~ = y * w, w = 10**U(-2, 2) drawn once per partition -- the A/B of class / sample weights against a run without
     the flag.
@@ -157,6 +159,7 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
     from erasurehead_amd.models.losses import LOSS_NAMES, weighted_kind
     from erasurehead_amd.ops import DenseGradPlan, SoftmaxGradPlan, get_precision
     from erasurehead_amd.ops.multimodel import MultiModelGradPlan
+    from erasurehead_amd.ops.ovr import OvrGradPlan
 
     layouts = {"naive": [[p] for p in range(8)], "agc": [[0, 1, 2]] * 3 + [[3, 4, 5]] * 3 + [[6, 7]] * 2}
     if layouts_only:
@@ -196,6 +199,24 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
                                 out.append(r)
                                 print(json.dumps(r), flush=True)
                                 del plan, G
+                            continue
+                        if loss == "ovr":
+                            for C in classes:
+                                ov = {p: (X, torch.randint(0, C, (rpp,), device="cuda").to(prec.acc))
+                                      for p, (X, _) in parts.items()}
+                                plan = OvrGradPlan([[(p, 1.0) for p in m] for m in msgs], ov, prec,
+                                                   LOSS_NAMES["logistic"], C, d)
+                                bC = torch.randn(plan.ld, device="cuda", dtype=prec.acc) * 0.01
+                                G = plan.out_buffer()[0]
+                                ms = _time(lambda: plan.run(bC, G), reps=20)
+                                distinct = 8 * nbytes / 1e12  # TB
+                                r = {"kernel": "grad_ovr_sweep", "precision": prec_name, "d": d, "n": n,
+                                     "layout": lay, "loss": "logistic", "classes": C, "tasks": plan.ntasks, "ms": ms,
+                                     "ms_per_model": ms / C, "distinct_TBps": distinct / ms * 1e3,
+                                     "copy_TBps": ceiling, "frac": distinct / ms * 1e3 / ceiling}
+                                out.append(r)
+                                print(json.dumps(r), flush=True)
+                                del plan, G, ov
                             continue
                         if loss == "softmax" and prec_name not in ("fp64", "fp32"):
                             print(json.dumps({"kernel": "grad_softmax_sweep", "precision": prec_name,
@@ -378,8 +399,9 @@ def main():
     ap.add_argument("--precs", default="fp64,fp32", help="--only sweep: precisions (fp64, fp32, bf16, fp32x64)")
     ap.add_argument("--loss", default="logistic",
                     help="--only sweep: losses timed on the same data, in order (logistic, least_squares, squared_hinge, "
-                         "softmax, multimodel = the M-model logistic kernel of an (alpha, lr) sweep)")
-    ap.add_argument("--classes", default="2", help="--only sweep --loss softmax: class counts, e.g. 2,4,7,8")
+                         "softmax, multimodel = the M-model logistic kernel of an (alpha, lr) sweep, ovr = the one-vs-rest "
+                         "logistic kernel)")
+    ap.add_argument("--classes", default="2", help="--only sweep --loss softmax / ovr: class counts, e.g. 2,4,7,8")
     ap.add_argument("--models", default="2", help="--only sweep --loss multimodel: model counts, e.g. 2,4,8")
     ap.add_argument("--weighted", action="store_true",
                     help="--only sweep / sparse: the weighted code of the loss on labels y * w, w = 10**U(-2, 2) (logistic, "
@@ -412,9 +434,9 @@ def main():
     from erasurehead_amd.models.losses import LOSS_CHOICES
 
     losses = tuple(a.loss.split(","))
-    if any(x not in LOSS_CHOICES and x != "multimodel" for x in losses):
-        ap.error(f"--loss: names from {sorted(LOSS_CHOICES) + ['multimodel']}")
-    if a.weighted and any(x in ("least_squares", "softmax", "multimodel") for x in losses):
+    if any(x not in LOSS_CHOICES and x not in ("multimodel", "ovr") for x in losses):
+        ap.error(f"--loss: names from {sorted(LOSS_CHOICES) + ['multimodel', 'ovr']}")
+    if a.weighted and any(x in ("least_squares", "softmax", "multimodel", "ovr") for x in losses):
         ap.error("--weighted: logistic or squared_hinge (no other kernel has a weighted instance)")
     out = []
     if a.only in (None, "dense"):
