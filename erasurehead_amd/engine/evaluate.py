@@ -35,17 +35,12 @@ import numpy as np
 import torch
 
 from ..data import io as dio
-from ..models.losses import LOGISTIC, SQUARED_HINGE, base_kind, is_classification, is_multiclass
+from ..models.losses import LOGISTIC
 from ..ops.eval import auc_columns, loss_sums, predictions, predictions_and_loss, sign_labels
 from ..utils import report
 from .trainer import TrainResult, Trainer
 
-
-SQHINGE_PREFIX = "sqhinge_"  # result files of squared-hinge runs (next to the logistic names)
-SOFTMAX_PREFIX = "softmax_"
-OVR_PREFIX = "ovr_"  # result files of one-vs-rest runs (before sqhinge_)
-WEIGHTED_PREFIX = "weighted_"  # result files of runs with class / sample weights
-SOFTMAX_P_ELEMS = 1 << 26  # logits held at once by the softmax evaluation (rounds are chunked to fit)
+SOFTMAX_P_ELEMS = 1 << 26  # logits held at once by the class evaluation (rounds are chunked to fit)
 
 
 @dataclass
@@ -60,22 +55,6 @@ class EvalResult:
     # non-zero data columns of every iterate: [R], sweep [R, M]; softmax and one-vs-rest: all C blocks
     nnz: Optional[np.ndarray] = None
     l1_penalty: Optional[np.ndarray] = None  # l1 * ||beta||_1 of every iterate, shaped like nnz
-
-
-def sparsity(trainer: Trainer, betaset: np.ndarray):
-    """(nnz, l1_penalty) of every iterate over the data columns: [R], or [R, M] for a sweep run (softmax counts
-    and one-vs-rest count over their C class blocks: they are one model with one lambda)."""
-    B = np.asarray(betaset, dtype=np.float64)
-    R, M = B.shape[0], getattr(trainer, "models", 1)
-    if M > 1:
-        blocks = B.reshape(R, M, trainer.ld_x)[:, :, : trainer.d_x]
-        l1 = np.asarray(trainer.sweep_l1, dtype=np.float64)
-        return np.count_nonzero(blocks, axis=2), np.abs(blocks).sum(axis=2) * l1
-    if is_multiclass(trainer.loss) or getattr(trainer, "ovr", False):
-        B = B.reshape(R, trainer.classes, trainer.ld_x)[:, :, : trainer.d_x].reshape(R, -1)
-    else:
-        B = B[:, : trainer.d]
-    return np.count_nonzero(B, axis=1), np.abs(B).sum(axis=1) * float(trainer.cfg.l1)
 
 
 def _nnz_line(l1: float, nnz: int, d: int) -> str:
@@ -95,16 +74,6 @@ def _weights_line(trainer: Trainer) -> str:
     spec = "none" if cw is None else cw if isinstance(cw, str) else "%g:%g" % tuple(cw)
     return ">> Weights: class_weight = %s, w+ = %g, w- = %g, sum w / n = %g" % (
         spec, trainer.class_weight[0], trainer.class_weight[1], trainer.weight_sum_over_n)
-
-
-def _result_names(trainer: Trainer) -> Dict[str, str]:
-    """The scheme's result names under the loss's prefixes: ``weighted_`` first, then ``sqhinge_``."""
-    names = trainer.scheme.output_names(trainer.cfg.fix_quirks)
-    if base_kind(trainer.loss) == SQUARED_HINGE:
-        names = {k: SQHINGE_PREFIX + v for k, v in names.items()}
-    if getattr(trainer, "weighted", False):
-        names = {k: WEIGHTED_PREFIX + v for k, v in names.items()}
-    return names
 
 
 def eval_partitions(trainer: Trainer):
@@ -130,109 +99,96 @@ def _train_chunks(trainer: Trainer, parts, prec, dev):
         yield resident[p]
 
 
-def _softmax_sums(X, y, B, classes: int, d_x: int):
-    """(CE sums [R], correct counts [R]) of the rows X, y for the models B [R * classes, ld_x]: logits from
-    the prediction GEMM (ops/eval.predictions), rounds chunked so the logits stay bounded."""
-    n, R = X.shape[0], B.shape[0] // classes
-    ce = torch.zeros(R, dtype=torch.float64)
-    hit = torch.zeros(R, dtype=torch.float64)
-    step = max(1, SOFTMAX_P_ELEMS // max(1, n * classes))
-    yl = y.to(X.device).long()
-    for r0 in range(0, R, step):
-        r1 = min(R, r0 + step)
-        Z = predictions(X, B[r0 * classes: r1 * classes], d_x).double().reshape(n, r1 - r0, classes)
-        zy = Z.gather(2, yl[:, None, None].expand(n, r1 - r0, 1))[:, :, 0]
-        ce[r0:r1] = (torch.logsumexp(Z, dim=2) - zy).sum(0).cpu()
-        hit[r0:r1] = (Z.argmax(dim=2) == yl[:, None]).double().sum(0).cpu()
-    return ce.numpy(), hit.numpy()
-
-
-def _ovr_sums(X, y, B, classes: int, d_x: int, kind: int):
-    """(loss sums [R], correct counts [R]) of the rows X, y (class indices) for the one-vs-rest models
-    B [R * classes, ld_x]: sum over rows and classes of l(y_k z_k) with l the logistic or the squared-hinge loss;
-    scores from the prediction GEMM, rounds chunked like _softmax_sums."""
+def _class_sums(X, y, B, classes: int, d_x: int, row_loss):
+    """(loss sums [R], correct counts [R]) of the rows X, y (class indices) for the models B [R * classes, ld_x]:
+    scores from the prediction GEMM (ops/eval.predictions), rounds chunked so the scores held at once stay bounded;
+    row_loss(Z [n, r, classes], y [n]) gives a chunk's loss sums [r]."""
     n, R = X.shape[0], B.shape[0] // classes
     tot = torch.zeros(R, dtype=torch.float64)
     hit = torch.zeros(R, dtype=torch.float64)
     step = max(1, SOFTMAX_P_ELEMS // max(1, n * classes))
     yl = y.to(X.device).long()
-    own = yl[:, None, None] == torch.arange(classes, device=X.device)[None, None, :]
     for r0 in range(0, R, step):
         r1 = min(R, r0 + step)
         Z = predictions(X, B[r0 * classes: r1 * classes], d_x).double().reshape(n, r1 - r0, classes)
-        m = torch.where(own, -Z, Z)  # -y_k z_k
-        if kind == LOGISTIC:
-            v = torch.clamp(m, min=0) + torch.log1p(torch.exp(-m.abs()))
-        else:
-            v = torch.clamp(1.0 + m, min=0) ** 2
-        tot[r0:r1] = v.sum(dim=(0, 2)).cpu()
+        tot[r0:r1] = row_loss(Z, yl).cpu()
         hit[r0:r1] = (Z.argmax(dim=2) == yl[:, None]).double().sum(0).cpu()
     return tot.numpy(), hit.numpy()
 
 
-def _evaluate_softmax(trainer: Trainer, res: TrainResult, log, write: bool) -> EvalResult:
-    """Softmax and one-vs-rest runs: a [classes][ld_x] model scored by its loss and the test accuracy."""
-    cfg, dev, prec = trainer.cfg, trainer.env.device, trainer.prec
-    C, d_x, ld_x = trainer.classes, trainer.d_x, trainer.ld_x
-    R = res.betaset.shape[0]
-    B = torch.from_numpy(np.ascontiguousarray(res.betaset)).to(dev).reshape(R * C, ld_x)
-    parts = eval_partitions(trainer)
-    if getattr(trainer, "ovr", False):
-        kind = trainer.loss
+def _softmax_sums(X, y, B, spec):
+    """Cross-entropy logsumexp(z) - z_y."""
+    def ce(Z, yl):
+        zy = Z.gather(2, yl[:, None, None].expand(Z.shape[0], Z.shape[1], 1))[:, :, 0]
+        return (torch.logsumexp(Z, dim=2) - zy).sum(0)
+    return _class_sums(X, y, B, spec.classes, spec.d_x, ce)
 
-        def sums(X, y):
-            return _ovr_sums(X, y, B, C, d_x, kind)
-        prefix = OVR_PREFIX + (SQHINGE_PREFIX if kind == SQUARED_HINGE else "")
-    else:
-        def sums(X, y):
-            return _softmax_sums(X, y, B, C, d_x)
-        prefix = SOFTMAX_PREFIX
+
+def _ovr_sums(X, y, B, spec):
+    """Sum over classes of l(y_k z_k), l the run's logistic or squared-hinge loss."""
+    def loss(Z, yl):
+        own = yl[:, None, None] == torch.arange(spec.classes, device=Z.device)[None, None, :]
+        m = torch.where(own, -Z, Z)  # -y_k z_k
+        if spec.loss == LOGISTIC:
+            v = torch.clamp(m, min=0) + torch.log1p(torch.exp(-m.abs()))
+        else:
+            v = torch.clamp(1.0 + m, min=0) ** 2
+        return v.sum(dim=(0, 2))
+    return _class_sums(X, y, B, spec.classes, spec.d_x, loss)
+
+
+_CLASS_SUMS = {"softmax": _softmax_sums, "ovr": _ovr_sums}
+
+
+def _evaluate_classes(trainer: Trainer, res: TrainResult, log, write: bool) -> EvalResult:
+    """Softmax and one-vs-rest runs: a [classes][ld_x] model scored by its loss and the test accuracy."""
+    cfg, dev, prec, spec = trainer.cfg, trainer.env.device, trainer.prec, trainer.model
+    R = res.betaset.shape[0]
+    B = torch.from_numpy(spec.rows(res.betaset)).to(dev)
+    parts = eval_partitions(trainer)
+    sums = _CLASS_SUMS[spec.kind]
     if cfg.verbose:
         log(report.total_time_line(res.total_time))
     tr_sum, n_train = np.zeros(R), 0
     for X, y in _train_chunks(trainer, parts, prec, dev):
-        s, _ = sums(X, y)
+        s, _ = sums(X, y, B, spec)
         tr_sum += s
         n_train += X.shape[0]
     Xt, yt = trainer.source.test(prec, dev)
-    te_sum, hits = sums(Xt, yt)
+    te_sum, hits = sums(Xt, yt, B, spec)
     n_test = Xt.shape[0]
     training_loss = tr_sum / max(1, n_train)
     testing_loss = te_sum / max(1, n_test)
     acc = hits / max(1, n_test)
-    nnz, pen = sparsity(trainer, res.betaset)
+    nnz, pen = spec.sparsity(res.betaset)
     if cfg.verbose:
         for i in range(R):
             log(report.softmax_line(i, training_loss[i], testing_loss[i], acc[i], res.timeset[i]))
-        if trainer.prox and R:
-            log(_nnz_line(cfg.l1, nnz[-1], C * d_x))
+        if spec.prox and R:
+            log(_nnz_line(spec.l1, nnz[-1], spec.classes * spec.d_x))
     files = None
     if write:
-        names = {k: prefix + v for k, v in trainer.scheme.output_names(cfg.fix_quirks).items()}
+        names = spec.result_names(trainer.scheme.output_names(cfg.fix_quirks))
         data_dir = getattr(trainer.source, "data_dir", None) or cfg.input_dir
         files = report.write_results(dio.results_dir(data_dir), names, training_loss, testing_loss, acc,
                                      res.timeset, res.worker_timeset, cfg.full_precision_outputs)
-        if trainer.prox:
+        if spec.prox:
             _write_nnz(files, nnz)
     if cfg.verbose:
         log(">>> Done")
     return EvalResult(training_loss, testing_loss, acc, n_train, n_test, files, nnz=nnz, l1_penalty=pen)
 
 
-def sweep_prefix(k: int) -> str:
-    return f"sweep{k}_"
-
-
-def _evaluate_sweep(trainer: Trainer, res: TrainResult, log, write: bool) -> EvalResult:
-    """Every model of a sweep run through the single-model evaluation: betaset [R, M * ld_x] as R * M models."""
-    cfg, dev, prec = trainer.cfg, trainer.env.device, trainer.prec
-    M, d_x, ld_x, kind = trainer.models, trainer.d_x, trainer.ld_x, trainer.loss
+def _evaluate_scalar(trainer: Trainer, res: TrainResult, log, write: bool) -> EvalResult:
+    """Runs of a scalar loss, M >= 1 models through one evaluation: betaset as R * M rows of the model matrix.  A
+    single model is M = 1 without a model axis, per-model header or prefix."""
+    cfg, dev, prec, spec = trainer.cfg, trainer.env.device, trainer.prec, trainer.model
+    M, d_x, kind = spec.models, spec.d_x, spec.loss
     R = res.betaset.shape[0]
-    B = torch.from_numpy(np.ascontiguousarray(res.betaset)).to(dev).reshape(R * M, ld_x)
+    B = torch.from_numpy(spec.rows(res.betaset)).to(dev)
     parts = eval_partitions(trainer)
-    weighted = getattr(trainer, "weighted", False)
     if cfg.verbose:
-        if weighted:
+        if spec.weighted:
             log(_weights_line(trainer))
         log(report.total_time_line(res.total_time))
         if trainer.scheme.logs_eval_loading and not trainer.source.is_sparse:
@@ -244,91 +200,46 @@ def _evaluate_sweep(trainer: Trainer, res: TrainResult, log, write: bool) -> Eva
     n_test = Xt.shape[0]
     training_loss = (np.asarray(sums) / max(1, n_train)).reshape(R, M)
     testing_loss = (np.asarray(tsum) / max(1, n_test)).reshape(R, M)
-    classify = is_classification(kind)
+    classify = spec.scoring == "auc"
     # weighted runs: the classes behind the weighted labels (an unweighted AUC, comparable across runs)
-    auc = (auc_columns(sign_labels(yt) if weighted else yt, P) if classify else np.zeros(R * M)).reshape(R, M)
-    nnz, pen = sparsity(trainer, res.betaset)
+    auc = (auc_columns(sign_labels(yt) if spec.weighted else yt, P) if classify else np.zeros(R * M)).reshape(R, M)
+    nnz, pen = spec.sparsity(res.betaset)
+    nnz_k = nnz.reshape(R, M)
     files = None
-    do_write = write and (classify or cfg.save_linear)
-    if do_write:
+    if write and (classify or cfg.save_linear):
         files = {}
         data_dir = getattr(trainer.source, "data_dir", None) or cfg.input_dir
-    for k in range(M):
+    for k, (header, prefix, l1) in enumerate(spec.scalar_models()):
         if cfg.verbose:
-            log(">> Model %d: alpha = %g, lr = %g" % (k, trainer.sweep_alpha[k], trainer.sweep_lr[k])
-                + (", l1 = %g" % trainer.sweep_l1[k] if trainer.prox else ""))
+            if header:
+                log(header)
             for i in range(R):
                 if classify:
                     log(report.logistic_line(i, training_loss[i, k], testing_loss[i, k], auc[i, k], res.timeset[i]))
                 else:
                     log(report.linear_line(i, training_loss[i, k], testing_loss[i, k], res.timeset[i]))
-            if trainer.prox and R:
-                log(_nnz_line(trainer.sweep_l1[k], nnz[-1, k], d_x))
-        if do_write:
-            names = {key: sweep_prefix(k) + v for key, v in _result_names(trainer).items()}
+            if spec.prox and R:
+                log(_nnz_line(l1, nnz_k[-1, k], d_x))
+        if files is not None:
+            names = spec.result_names(trainer.scheme.output_names(cfg.fix_quirks), prefix)
             out = report.write_results(dio.results_dir(data_dir), names, training_loss[:, k], testing_loss[:, k],
                                        auc[:, k], res.timeset, res.worker_timeset, cfg.full_precision_outputs)
-            files.update({sweep_prefix(k) + key: v for key, v in out.items()})
-            if trainer.prox:
-                _write_nnz(files, nnz[:, k], sweep_prefix(k) + "nnz")
+            files.update({prefix + key: v for key, v in out.items()})
+            if spec.prox:
+                _write_nnz(files, nnz_k[:, k], prefix + "nnz")
     final = testing_loss[-1] if R else np.zeros(M)
-    best = int(np.argmin(np.where(np.isfinite(final), final, np.inf)))
+    best = spec.best(final)
     if cfg.verbose:
-        log(">> Best model: %d (alpha = %g, lr = %g, final test loss %g)"
-            % (best, trainer.sweep_alpha[best], trainer.sweep_lr[best], final[best]))
+        if best is not None:
+            log(">> Best model: %d (alpha = %g, lr = %g, final test loss %g)"
+                % (best, spec.sweep_alpha[best], spec.sweep_lr[best], final[best]))
         log(">>> Done")
-    return EvalResult(training_loss, testing_loss, auc, n_train, n_test, files, best, nnz=nnz, l1_penalty=pen)
+    return EvalResult(spec.per_model(training_loss), spec.per_model(testing_loss), spec.per_model(auc), n_train,
+                      n_test, files, best, nnz=nnz, l1_penalty=pen)
 
 
 def evaluate(trainer: Trainer, res: TrainResult, log=None, write: bool = True) -> EvalResult:
     log = log or report.log
-    if is_multiclass(trainer.loss) or getattr(trainer, "ovr", False):
-        return _evaluate_softmax(trainer, res, log, write)
-    if getattr(trainer, "models", 1) > 1:
-        return _evaluate_sweep(trainer, res, log, write)
-    cfg = trainer.cfg
-    dev = trainer.env.device
-    prec = trainer.prec
-    d, ld = trainer.d, trainer.ld
-    R = res.betaset.shape[0]
-    B = torch.zeros((R, ld), dtype=torch.float64, device=dev)
-    B[:, :d] = torch.from_numpy(res.betaset).to(dev)
-    kind = trainer.loss
-    parts = eval_partitions(trainer)
-    weighted = getattr(trainer, "weighted", False)
-    if cfg.verbose:
-        if weighted:
-            log(_weights_line(trainer))
-        log(report.total_time_line(res.total_time))
-        if trainer.scheme.logs_eval_loading and not trainer.source.is_sparse:
-            for p in parts:
-                log(">> Loaded %d" % (p + 1))
-    sums, n_train = loss_sums(_train_chunks(trainer, parts, prec, dev), B, d, kind, acc=prec)
-    Xt, yt = trainer.source.test(prec, dev)
-    P, tsum = predictions_and_loss(Xt, yt, B, d, kind, acc=prec)
-    n_test = Xt.shape[0]
-    training_loss = sums / max(1, n_train)
-    testing_loss = tsum / max(1, n_test)
-    classify = is_classification(kind)
-    # weighted runs: the classes behind the weighted labels (an unweighted AUC, comparable across runs)
-    auc = auc_columns(sign_labels(yt) if weighted else yt, P) if classify else np.zeros(R)
-    nnz, pen = sparsity(trainer, res.betaset)
-    if cfg.verbose:
-        for i in range(R):
-            if classify:
-                log(report.logistic_line(i, training_loss[i], testing_loss[i], auc[i], res.timeset[i]))
-            else:
-                log(report.linear_line(i, training_loss[i], testing_loss[i], res.timeset[i]))
-        if trainer.prox and R:
-            log(_nnz_line(cfg.l1, nnz[-1], d))
-    files = None
-    if write and (classify or cfg.save_linear):
-        names = _result_names(trainer)
-        data_dir = getattr(trainer.source, "data_dir", None) or cfg.input_dir
-        files = report.write_results(dio.results_dir(data_dir), names, training_loss, testing_loss, auc,
-                                     res.timeset, res.worker_timeset, cfg.full_precision_outputs)
-        if trainer.prox:
-            _write_nnz(files, nnz)
-    if cfg.verbose:
-        log(">>> Done")
-    return EvalResult(training_loss, testing_loss, auc, n_train, n_test, files, nnz=nnz, l1_penalty=pen)
+    if trainer.model.scoring == "accuracy":
+        return _evaluate_classes(trainer, res, log, write)
+    return _evaluate_scalar(trainer, res, log, write)

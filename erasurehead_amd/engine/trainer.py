@@ -46,19 +46,16 @@ import torch
 
 from .._ext import native as native_ext
 from .loops import LoopInputs, release_override, select_release_form, select_round_loop
+from .model import ModelSpec, UpdateSchedule
 from ..codes.schemes import Arrival, Scheme, SchemeError, make_scheme, scheme_key
 from ..config import RunConfig
 from ..data import io as dio
 from ..data.source import (DataSource, FileSource, SyntheticSource, WeightedSource, balanced_class_weights,
                            check_weights)
-from ..models.losses import (LEAST_SQUARES, LOGISTIC, LOSS_CHOICES, SOFTMAX, SQUARED_HINGE, UpdateRule, check_classes,
-                             is_classification, weighted_kind)
-from ..ops.grad import DenseGradPlan, SharedGradPlan, SparseGradPlan
-from ..ops.softmax import SoftmaxGradPlan
-from ..ops.multimodel import MultiModelGradPlan
-from ..ops.ovr import OvrGradPlan
+from ..models.losses import UpdateRule
+from ..ops.blockplan import BlockGradPlan
+from ..ops.grad import SharedGradPlan, SparseGradPlan
 from ..ops.precision import get_precision
-from ..ops.update import combine_update, combine_update_blocks, combine_update_prox
 from ..parallel.collector import ArrivalCollector
 from ..parallel.dist import DistEnv
 from ..parallel.placement import make_shards, place_spread, place_units
@@ -128,18 +125,38 @@ class Trainer:
         self.device_loop: Optional[str] = None  # set by the native master loop when rounds ran device-driven
         self.rank_stats: Dict[str, float] = {}  # per-rank breakdown of the last run (rank_report)
         self._setup_scheme(scheme, source)
+        self.prec = get_precision(cfg.precision)
+        # what the run's source will be (_setup_data builds one where none is given): generated data is dense
+        sparse = source.is_sparse if source is not None else (cfg.data != "synthetic" and bool(cfg.is_real))
+        self.model = ModelSpec.resolve(cfg, self.scheme, sparse, getattr(source, "weights", None) is not None,
+                                       self.prec, bool(env.gpu))
         warm = self._start_eval_warmup()
         self._setup_data(source)
         self._setup_buffers()
         if warm is not None:
             warm.join()
 
+    # the model's facts, as the tests, tools/ and bench.py read them off the trainer
+    loss = property(lambda self: self.model.loss)
+    weighted = property(lambda self: self.model.weighted)
+    classes = property(lambda self: self.model.classes)
+    ovr = property(lambda self: self.model.ovr)
+    blocked = property(lambda self: self.model.blocked)
+    models = property(lambda self: self.model.models)
+    sweep_alpha = property(lambda self: self.model.sweep_alpha)
+    sweep_lr = property(lambda self: self.model.sweep_lr)
+    sweep_l1 = property(lambda self: self.model.sweep_l1)
+    prox = property(lambda self: self.model.prox)
+    d_x = property(lambda self: self.model.d_x)
+    ld_x = property(lambda self: self.model.ld_x)
+    d = property(lambda self: self.model.d)
+    ld = property(lambda self: self.model.ld)
+
     # ------------------------------------------------------------------------------ setup
     def _start_eval_warmup(self):
         """Master on a GPU, classification runs (logistic, squared hinge) that will be evaluated: load the AUC path's code objects on a
         side thread while the data is generated / loaded (ops/eval.warm_auc; 0.6 s cold)."""
-        if not (self.env.is_master and self.env.gpu and self.cfg.evaluate and is_classification(self.loss)) \
-                or self.ovr:  # a one-vs-rest run is scored by accuracy, not by AUC
+        if not (self.env.is_master and self.env.gpu and self.cfg.evaluate and self.model.scoring == "auc"):
             return None
         import threading
 
@@ -174,47 +191,9 @@ class Trainer:
                 scheme = make_scheme(self.key, W, cfg.n_stragglers, cfg.n_rows, cfg.num_collect, cfg.partitions,
                                      cfg.allow_uneven_groups, None, B)
         self.scheme = scheme
-        if cfg.loss == "auto":
-            self.loss = LEAST_SQUARES if (cfg.dataset == "kc_house_data" and scheme.has_linear) else LOGISTIC
-        else:
-            if cfg.loss not in LOSS_CHOICES:
-                raise ValueError(f"unknown loss {cfg.loss!r}: auto or one of {sorted(LOSS_CHOICES)}")
-            self.loss = LOSS_CHOICES[cfg.loss]
-        # class / sample weights: the labels carry them (data/source.py WeightedSource) and the plan runs the weighted
-        # code of the loss; without them the run takes exactly the code paths it takes without the feature
-        self.weighted = cfg.weighted or getattr(source, "weights", None) is not None
-        if self.weighted:
-            if self.loss not in (LOGISTIC, SQUARED_HINGE):
-                name = {LEAST_SQUARES: "least squares", SOFTMAX: "softmax"}.get(self.loss, str(self.loss))
-                raise ValueError(f"--class-weight / --sample-weights: not supported with the {name} loss (the label "
-                                 f"cannot carry the weight there); logistic or squared_hinge")
-            self.loss = weighted_kind(self.loss)
-        # multi-class softmax: the model is [classes][ld_x] flattened (ops/softmax.py); 1 for every other loss
-        self.classes = check_classes(cfg.classes or 2) if self.loss == SOFTMAX else 1
-        # one-vs-rest (--ovr C): C binary models of the scalar loss in the same [classes][ld_x] layout (ops/ovr.py);
-        # self.loss stays the binary loss.  blocked: the model is class-major blocks, as softmax's is
-        self.ovr = cfg.ovr is not None
-        if self.ovr:
-            if self.loss == LEAST_SQUARES:
-                raise ValueError("--ovr: --loss auto resolves to least squares for this run, which has no "
-                                 "one-vs-rest form; name --loss logistic or squared_hinge")
-            if self.weighted:  # (a source that brings sample weights of its own; the flags are the config's to reject)
-                raise ValueError("--ovr: class / sample weights are not supported (the labels are class indices and "
-                                 "cannot carry a weight)")
-            self.classes = check_classes(cfg.ovr)
-        self.blocked = self.loss == SOFTMAX or self.ovr
-        # (alpha, lr) sweep: M models of one scalar loss, the model [M][ld_x] flattened (ops/multimodel.py)
-        sweep = cfg.sweep()
-        self.models = len(sweep) if sweep else 1
-        self.sweep_alpha = [a for a, _ in sweep] if sweep else None
-        self.sweep_lr = [x for _, x in sweep] if sweep else None
         self.rule_kind, self.rule_k = scheme.rule()
         self.update = UpdateRule("AGD" if scheme.fixed_agd else cfg.update_rule, cfg.alpha_value, cfg.n_rows,
                                  scheme.grad_scale(), float(cfg.l1))
-        # L1 / elastic net: a soft threshold after the master's update (ops/update.py combine_update_prox), taken
-        # only when some lambda > 0 -- a run whose lambdas are all 0 runs exactly the code it ran without them
-        self.sweep_l1 = cfg.sweep_l1s()
-        self.prox = any(x > 0 for x in (self.sweep_l1 if sweep else [cfg.l1]))
         self.drain_mode = cfg.drain or ("all" if scheme.drain else "carry")
         self.drain = self.drain_mode == "all"
         self.skip_stale = self.drain_mode == "lazy"
@@ -266,11 +245,10 @@ class Trainer:
 
     def _setup_data(self, source: Optional[DataSource]):
         cfg, sch = self.cfg, self.scheme
-        self.prec = get_precision(cfg.precision)
         if source is None:
             if cfg.data == "synthetic":
                 source = SyntheticSource(cfg.n_rows, cfg.n_cols, sch.n_partition_files, cfg.data_seed,
-                                         classes=self.classes if self.blocked else None)
+                                         classes=self.model.label_classes)
             else:
                 data_dir = dio.dataset_dir(cfg.input_dir, cfg.is_real, cfg.dataset, cfg.n_rows, cfg.n_cols)
                 data_dir = data_dir + sch.data_subdir()
@@ -279,22 +257,6 @@ class Trainer:
         if self.weighted:
             source = self._weighted_source(source)
         self.source = source
-        # d_x / ld_x: the data's columns and row stride; d / ld: everything model-sized (beta, messages,
-        # history).  They differ only for softmax and one-vs-rest, whose model is the flattened [classes][ld_x].
-        self.d_x = cfg.n_cols
-        self.ld_x = self.prec.ld(self.d_x)
-        self.d, self.ld = self.d_x, self.ld_x
-        if self.loss == SOFTMAX:
-            self.d = self.ld = self.classes * self.ld_x
-            SoftmaxGradPlan.check_supported(self.prec, self.classes, source.is_sparse)  # before any load
-        if self.ovr:
-            self.d = self.ld = self.classes * self.ld_x
-            OvrGradPlan.check_supported(self.prec, self.loss, self.classes, source.is_sparse, self.ld_x,
-                                        bool(self.env.gpu))  # before any load
-        if self.models > 1:
-            self.d = self.ld = self.models * self.ld_x
-            MultiModelGradPlan.check_supported(self.prec, self.loss, self.models, source.is_sparse, self.ld_x,
-                                               bool(self.env.gpu))  # before any load
         dev = self.env.device
         needed = sorted({p for m in self.local_msgs for p, _ in m.segments})
         if not source.is_sparse and self.env.gpu:
@@ -304,27 +266,7 @@ class Trainer:
         self.load_seconds = time.perf_counter() - t0
         if self.weighted:
             self._weight_sum(parts)
-        segs = [m.segments for m in self.local_msgs]
-
-        def make_plan(messages):
-            if self.loss == SOFTMAX:  # shares the distinct partitions by itself: --share-partitions changes nothing
-                return SoftmaxGradPlan(messages, parts, self.prec, self.classes, self.d_x)
-            if self.ovr:  # likewise
-                return OvrGradPlan(messages, parts, self.prec, self.loss, self.classes, self.d_x)
-            if self.models > 1:  # likewise: every distinct partition once, whatever --share-partitions says
-                return MultiModelGradPlan(messages, parts, self.prec, self.loss, self.models, self.d_x)
-            if source.is_sparse:
-                return SparseGradPlan(messages, parts, self.prec, self.loss, self.d, device=dev)
-            kw = {"target_tasks": cfg.tasks} if cfg.tasks else {}
-            if cfg.pack == "off":
-                kw["pack"] = False
-            return DenseGradPlan(messages, parts, self.prec, self.loss, self.d, **kw)
-
-        share = cfg.share_partitions and not self.blocked and self.models == 1
-        if share and SharedGradPlan.worthwhile(segs, lambda p: parts[p][0].shape[0]):
-            self.plan = SharedGradPlan(segs, make_plan)
-        else:
-            self.plan = make_plan(segs)
+        self.plan = self.model.make_plan([m.segments for m in self.local_msgs], parts, cfg, dev)
         self._parts = parts
 
     def _weighted_source(self, source: DataSource) -> WeightedSource:
@@ -474,35 +416,18 @@ class Trainer:
         counts = collections.Counter(p for m in self.local_msgs for p, _ in m.segments)
         if not counts or max(counts.values()) < 2:
             return "none"
-        if isinstance(plan, (SharedGradPlan, SparseGradPlan, SoftmaxGradPlan, MultiModelGradPlan, OvrGradPlan)):
+        if isinstance(plan, (SharedGradPlan, SparseGradPlan, BlockGradPlan)):
             return "encoded"
         return "separate"
 
     # --------------------------------------------------------------------------- helpers
     def _init_beta(self):
         """beta_0: randn (naive/replication/approx) or zeros (ref §2.2 'Per-scheme beta init')."""
-        d = self.d
-        nb = self.classes * self.d_x  # softmax, one-vs-rest: classes * d_x values, scattered into [classes][:d_x] below
-        if self.scheme.init_zero:
-            b0 = np.zeros(nb)
-        elif self.cfg.seed is not None:
-            b0 = np.random.RandomState(self.cfg.seed + 1).randn(nb)
-        else:
-            b0 = np.random.randn(nb)
-        if self.blocked:  # the padding columns of every class block stay zero
-            full = np.zeros((self.classes, self.ld_x))
-            full[:, : self.d_x] = b0.reshape(self.classes, self.d_x)
-            b0 = full.ravel()
-        if self.models > 1:  # every model starts from the single-model run's beta_0; padding columns stay zero
-            full = np.zeros((self.models, self.ld_x))
-            full[:, : self.d_x] = b0
-            b0 = full.ravel()
-        self.beta.zero_()
-        self.beta[:d] = torch.from_numpy(b0).to(self.beta.device)
+        packed = self.model.beta0(self.scheme.init_zero, self.cfg.seed)  # [ld], padding columns zero
+        self.beta.copy_(torch.from_numpy(packed).to(self.beta.device))
         self.u.zero_()
-        self.beta_in[0].zero_()
-        self.beta_in[0, :d] = self.beta[:d].to(self.beta_in.dtype)
-        self.beta0 = b0
+        self.beta_in[0].copy_(self.beta.to(self.beta_in.dtype))
+        self.beta0 = packed[: self.d]
 
     def _sync(self):
         if self.env.gpu:
@@ -725,8 +650,7 @@ class Trainer:
     def _master_loop(self, timed_start, log, start: int = 0) -> TrainResult:
         cfg, env, sch = self.cfg, self.env, self.scheme
         R, W, K = cfg.num_itrs, cfg.n_workers, self.K
-        eta = cfg.eta()
-        sweep_eta = cfg.sweep_etas()  # [M, R] in a sweep run
+        sched = self._update_schedule()
         col = ArrivalCollector(W, sch.group_of, sch.n_groups, env.gpu, cfg.tie_seed_value)
         col.set_shards(self.n_shards)
         col.set_skip_stale(self.skip_stale)
@@ -799,24 +723,7 @@ class Trainer:
                 if env.gpu and not cfg.sync_update:
                     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     ev0.record(self.cs)
-                if self.prox:  # the update, then the soft threshold eta_i * l1 (per model in a sweep)
-                    if self.models > 1:
-                        decay, gm, l2, theta, code = self.update.block_coeffs(i, sweep_eta[:, i], self.sweep_alpha)
-                        thr = self.update.block_thresholds(i, sweep_eta[:, i], self.sweep_l1)
-                    else:
-                        decay, gm, l2, theta, code = self.update.coeffs(i, float(eta[i]))
-                        decay, gm, l2, thr = [decay], [gm], [l2], [self.update.threshold(i, float(eta[i]))]
-                    combine_update_prox(msgs, coefs, self.beta, self.u, self.ld_x if self.models > 1 else self.ld,
-                                        self.d_x if self.models > 1 else self.d, decay, gm, l2, thr, theta, code,
-                                        hist=self.hist[i], beta_w=self.beta_in[i + 1])
-                elif self.models > 1:  # every model block with its own (alpha_k, lr_k)
-                    decay, gm, l2, theta, code = self.update.block_coeffs(i, sweep_eta[:, i], self.sweep_alpha)
-                    combine_update_blocks(msgs, coefs, self.beta, self.u, self.ld_x, self.d_x, decay, gm, l2, theta,
-                                          code, hist=self.hist[i], beta_w=self.beta_in[i + 1])
-                else:
-                    decay, gm, l2, theta, code = self.update.coeffs(i, float(eta[i]))
-                    combine_update(msgs, coefs, self.beta, self.u, self.d, decay, gm, l2, theta, code,
-                                   hist=self.hist[i], beta_w=self.beta_in[i + 1])
+                sched.apply(i, msgs, coefs, self.beta, self.u, self.hist[i], self.beta_in[i + 1])
                 if env.gpu:
                     if cfg.sync_update:
                         self.upd_ev.record(self.cs)
@@ -854,11 +761,22 @@ class Trainer:
         a0 = (timed_start or start) - start
         self.rank_stats.update({f"{k}_us": float(1e6 * np.mean(v[a0:])) for k, v in self.timer.t.items()
                                 if len(v) > a0})
+        return self._result(timeset, worker_timeset, loop_time, total, timeouts, arrivals_log, timed_start, t_timed0,
+                            t_timed1)
+
+    def _update_schedule(self) -> UpdateSchedule:
+        """The run's per-round update coefficients (engine/model.py), for either master loop."""
+        cfg = self.cfg
+        return UpdateSchedule.build(self.update, cfg.num_itrs, cfg.eta(), cfg.sweep_etas(), self.model)
+
+    def _result(self, timeset, worker_timeset, loop_time, total, timeouts, arrivals_log, timed_start, t_timed0,
+                t_timed1) -> TrainResult:
+        """What either master loop returns: the stored trajectory and the books it kept."""
         res = TrainResult(self.key, self.hist[:, : self.d].double().cpu().numpy(), timeset, worker_timeset, loop_time,
                           total, timeouts=timeouts, phases=self.timer.summary(), arrivals=arrivals_log)
         if t_timed0 is not None:
             res.timed_seconds = t_timed1 - t_timed0
-            res.timed_rounds = R - timed_start
+            res.timed_rounds = self.cfg.num_itrs - timed_start
         return res
 
     def rank_report(self) -> Dict[str, object]:
@@ -883,12 +801,8 @@ class Trainer:
                                   "workers": sorted({int(m.worker) for m in self.local_msgs}),
                                   "messages": len(self.local_msgs),
                                   "partitions": len({p for m in self.local_msgs for p, _ in m.segments})}
-        if self.models > 1:
-            rep.update(models=self.models, sweep_alpha=list(self.sweep_alpha), sweep_lr=list(self.sweep_lr))
-        if self.ovr:
-            rep.update(ovr=True, classes=self.classes)
-        rep.update(l1=list(self.sweep_l1) if self.models > 1 else float(self.cfg.l1), prox=bool(self.prox))
-        rep.update(weighted=bool(self.weighted), class_weight=list(self.class_weight) if self.weighted else None,
+        rep.update(self.model.report())
+        rep.update(class_weight=list(self.class_weight) if self.weighted else None,
                    weight_sum_over_n=self.weight_sum_over_n)
         rep.update({k: (round(float(v), 2) if isinstance(v, (int, float)) and not isinstance(v, bool) else v)
                     for k, v in self.rank_stats.items() if v is not None})
@@ -956,23 +870,9 @@ class Trainer:
             pump.set_sources(srcs)
             if self._device_waits(tx):  # drain on the device: beta(i+1) leaves as the last message lands
                 self.rank_stats["device_drain"] = bool(pump.set_drain_flags(srcs))
-        eta = cfg.eta()
-        co = [self.update.coeffs(i, float(eta[i])) for i in range(R)]
         delay_table = self.delay_table()
-        pump.set_schedule([c[0] for c in co], [c[1] for c in co], [c[2] for c in co], [c[3] for c in co],
-                          co[0][4] if co else 0, [float(x) for x in delay_table.ravel()], self.rule_kind,
-                          self.rule_k, bool(self.drain))
-        if self.models > 1:  # per-model (decay, gm, l2), flat [R * M]; theta and the rule are common
-            se = cfg.sweep_etas()
-            bco = [self.update.block_coeffs(i, se[:, i], self.sweep_alpha) for i in range(R)]
-            pump.set_block_schedule(self.models, self.ld_x, self.d_x, [x for c in bco for x in c[0]],
-                                    [x for c in bco for x in c[1]], [x for c in bco for x in c[2]])
-        if self.prox:  # soft thresholds [R] or [R * M]; the rounds then stay off both fused update paths
-            if self.models > 1:
-                thr = [t for i in range(R) for t in self.update.block_thresholds(i, se[:, i], self.sweep_l1)]
-            else:
-                thr = [self.update.threshold(i, float(eta[i])) for i in range(R)]
-            pump.set_prox_schedule(thr)
+        self._update_schedule().install(pump, [float(x) for x in delay_table.ravel()], self.rule_kind, self.rule_k,
+                                        bool(self.drain))
         if self.physical:  # remote messages are really late: the collector applies no virtual delay to them
             pump.set_remote_delays([float(x) for x in self._remote_delays(delay_table).ravel()])
         if self._clocks and tx is not None and (self.physical or cfg.device_records):
@@ -1134,13 +1034,9 @@ class Trainer:
         self._sync()
         self._closing_barrier()
         total = time.perf_counter() - orig_start
-        res = TrainResult(self.key, self.hist[:, : self.d].double().cpu().numpy(), timeset, worker_timeset, loop_time,
-                          total, timeouts=timeouts, phases=self.timer.summary(), arrivals=arrivals_log)
-        if t_timed0 is not None:
-            res.timed_seconds = t_timed1 - t_timed0
-            res.timed_rounds = R - timed_start
         del pump
-        return res
+        return self._result(timeset, worker_timeset, loop_time, total, timeouts, arrivals_log, timed_start, t_timed0,
+                            t_timed1)
 
     @staticmethod
     def _shared_gpu(tx) -> bool:
@@ -1349,35 +1245,7 @@ class Trainer:
         nxt = int(st["next_round"])
         if not 0 < nxt <= self.cfg.num_itrs:
             raise ValueError(f"checkpoint next_round {nxt} outside (0, {self.cfg.num_itrs}]")
-        if self.models > 1 or "sweep_alpha" in st:  # a sweep resumes only as the same sweep
-            want = (self.sweep_alpha, self.sweep_lr) if self.models > 1 else (None, None)
-            have = tuple(None if st.get(k) is None else [float(x) for x in st[k]] for k in ("sweep_alpha", "sweep_lr"))
-            if have != want:
-                raise ValueError(f"checkpoint {path} was written by a run with sweep lists alphas = {have[0]}, "
-                                 f"lrs = {have[1]}; this run has alphas = {want[0]}, lrs = {want[1]}")
-        # the L1 strength likewise; a checkpoint without the key was written without an L1 penalty
-        have_l1 = float(st.get("l1", 0.0))
-        if have_l1 != float(self.cfg.l1):
-            raise ValueError(f"checkpoint {path} was written by a run with l1 = {have_l1:g}; this run has "
-                             f"l1 = {float(self.cfg.l1):g}")
-        if self.models > 1:
-            have_l1s = [float(x) for x in st["sweep_l1"]] if st.get("sweep_l1") is not None else [0.0] * self.models
-            if have_l1s != [float(x) for x in self.sweep_l1]:
-                raise ValueError(f"checkpoint {path} was written by a run with sweep_l1 = {have_l1s}; this run has "
-                                 f"sweep_l1 = {list(self.sweep_l1)}")
-        # one-vs-rest likewise; a checkpoint without the key was written by a run without --ovr
-        have_ovr = st.get("ovr")
-        if have_ovr != self.cfg.ovr:
-            raise ValueError(f"checkpoint {path} was written by a run with ovr = {have_ovr}; this run has "
-                             f"ovr = {self.cfg.ovr} (--ovr)")
-        # class / sample weights likewise; a checkpoint without the key was written by an unweighted run
-        have_w = st.get("weights")
-        if have_w != self.weight_spec:
-            raise ValueError(f"checkpoint {path} was written by a run with weights = {have_w}; this run has "
-                             f"weights = {self.weight_spec} (--class-weight / --sample-weights)")
-        ld = self.ld
-        if st["beta"].numel() != ld:
-            raise ValueError("checkpoint beta has a different feature dimension")
+        self.model.check_checkpoint(st, path, self.weight_spec)
         dev = self.beta.device
         self.beta.copy_(st["beta"].to(dev))
         self.u.copy_(st["u"].to(dev))
@@ -1397,15 +1265,7 @@ class Trainer:
         state = {"next_round": next_round, "beta": self.beta.cpu(), "u": self.u.cpu(),
                  "hist": self.hist[:next_round].cpu(), "timeset": torch.from_numpy(timeset[:next_round].copy()),
                  "worker_timeset": torch.from_numpy(worker_timeset[:next_round].copy()), "scheme": self.key}
-        if self.models > 1:
-            state["sweep_alpha"] = [float(a) for a in self.sweep_alpha]
-            state["sweep_lr"] = [float(x) for x in self.sweep_lr]
-            state["sweep_l1"] = [float(x) for x in self.sweep_l1]
-        state["l1"] = float(self.cfg.l1)
-        if self.weighted:
-            state["weights"] = self.weight_spec
-        if self.ovr:
-            state["ovr"] = int(self.cfg.ovr)
+        state.update(self.model.checkpoint_state(self.weight_spec))
         if getattr(self.scheme, "B", None) is not None:
             state["B"] = torch.from_numpy(np.ascontiguousarray(self.scheme.B, dtype=np.float64))
         tmp = path + ".tmp"

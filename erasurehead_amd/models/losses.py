@@ -43,7 +43,7 @@ SQUARED_HINGE = 2
 SOFTMAX = 3
 # weighted logistic / squared hinge (csrc/kernels/common.h kLogisticW / kSquaredHingeW): the label carries the row's
 # weight, y~ = s * w with the class s the sign BIT of y~ and w = |y~| >= 0.  The engine selects them when a run has
-# class or sample weights (engine/trainer.py); no --loss name maps to them.
+# class or sample weights (engine/model.py); no --loss name maps to them.
 LOGISTIC_W = 4
 SQUARED_HINGE_W = 5
 _WEIGHTED = {LOGISTIC: LOGISTIC_W, SQUARED_HINGE: SQUARED_HINGE_W}

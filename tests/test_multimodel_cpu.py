@@ -15,6 +15,7 @@ from erasurehead_amd.codes import make_scheme, scheme_key
 from erasurehead_amd.config import RunConfig
 from erasurehead_amd.data.source import ArraySource
 from erasurehead_amd.engine import Trainer, evaluate
+from erasurehead_amd.engine.model import ModelSpec
 from erasurehead_amd.models import losses
 from erasurehead_amd.ops import get_precision
 from erasurehead_amd.ops.multimodel import MultiModelGradPlan
@@ -134,6 +135,34 @@ def test_pack_unpack_round_trip():
         losses.sweep_unpack(flat, 4, 33)
     with pytest.raises(ValueError):
         losses.sweep_pack(B, 32)
+
+
+@pytest.mark.parametrize("kind, kw, blocks", [
+    ("single", {}, 1), ("softmax", dict(loss="softmax", classes=3), 3), ("ovr", dict(ovr=3), 3),
+    ("sweep", dict(sweep_alpha=ALPHAS, sweep_lr=LRS), 3)])
+def test_model_spec_lays_out_every_kind(kind, kw, blocks):
+    cfg, _, sch, _ = make(CASES["naive"], **kw)
+    prec = get_precision("fp64")
+    spec = ModelSpec.resolve(cfg, sch, False, False, prec, False)
+    ld = blocks * 34
+    assert (spec.kind, spec.d_x, spec.ld_x, spec.d, spec.ld, spec.blocks) == (kind, 33, 34, 33 if kind == "single" else ld,
+                                                                             ld, blocks)
+    b0 = spec.beta0(False, cfg.seed)
+    assert b0.shape == (ld,) and np.all(b0.reshape(blocks, 34)[:, 33:] == 0.0)
+    assert np.all(b0.reshape(blocks, 34)[:, :33] != 0.0)
+    if kind == "sweep":  # every block is the single-model beta_0 of the same seed
+        single = ModelSpec.resolve(make(CASES["naive"])[0], sch, False, False, prec, False).beta0(False, cfg.seed)
+        for k in range(3):
+            np.testing.assert_array_equal(b0.reshape(3, 34)[k], single)
+    if kind in ("softmax", "ovr"):  # classes * d_x values drawn in one call
+        np.testing.assert_array_equal(spec.unpack(b0[None])[0].ravel(), np.random.RandomState(cfg.seed + 1).randn(3 * 33))
+    np.testing.assert_array_equal(spec.beta0(True, cfg.seed), np.zeros(ld))
+    x = np.random.RandomState(1).randn(5, blocks, 33)
+    flat = spec.pack(x)
+    assert flat.shape == (5, ld) and np.all(flat.reshape(5, blocks, 34)[:, :, 33:] == 0.0)
+    np.testing.assert_array_equal(spec.unpack(flat), x)
+    np.testing.assert_array_equal(spec.unpack(flat[:, : spec.d]), x)  # a stored trajectory is [R, d]
+    np.testing.assert_array_equal(spec.rows(flat[:, : spec.d]), flat.reshape(5 * blocks, 34))
 
 
 def test_padding_stays_zero_over_a_run():
