@@ -802,6 +802,7 @@ class SparseGradPlan:
         self.blocks = []
         for p in self.basis:
             A, y = partitions[p]
+            self._check_partition(p, A, y, d)
             A = sps.csr_matrix(A)
             if A.shape[1] > d:
                 raise ValueError("partition has more columns than d")
@@ -844,6 +845,25 @@ class SparseGradPlan:
             else:
                 dev_blocks = self.blocks
             self._build_device(X, use_ell, dev_blocks)
+
+    @staticmethod
+    def _check_partition(p, A, y, d: int) -> None:
+        """scipy's (data, indices, indptr) constructor does not look at the indices, and a column index >= d (what
+        a wrong d produces) reaches tocsc() in csc_tables unchecked, where it can crash the interpreter: check
+        the CSR arrays as they are, before anything else touches them."""
+        import scipy.sparse as sps
+
+        if sps.isspmatrix_csr(A):
+            indptr, indices = np.asarray(A.indptr), np.asarray(A.indices)
+            ok = indptr.ndim == 1 and indptr.size == A.shape[0] + 1 and indptr[0] == 0 and np.all(np.diff(indptr) >= 0)
+            if not ok or indptr[-1] > min(indices.size, np.asarray(A.data).size):
+                raise ValueError(f"partition {p}: indptr must be non-decreasing from 0 to the number of entries")
+            idx = indices[: int(indptr[-1])]
+            if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= d):
+                raise ValueError(f"partition {p}: column indices must be in [0, {d}) "
+                                 f"(found {int(idx.min())} .. {int(idx.max())})")
+        if not np.all(np.isfinite(np.asarray(y, dtype=np.float64))):
+            raise ValueError(f"partition {p}: labels must be finite")
 
     def _merge_units(self):
         """The FRC / AGC message sets as device units (see UNIT_ROWS), or None: every coefficient 1, some

@@ -128,7 +128,7 @@ def column_ratio(got, ref, bound):
     return float(np.max(q)) if q.size else 0.0
 
 
-def check_columns(got, ref, bound, what=""):
+def check_columns(got, ref, bound, what="", k=K):
     """Every column within its own bound; the message names the worst column."""
     assert np.all(np.isfinite(np.asarray(got, np.float64))), f"{what}: non-finite entries (unwritten or overflowed)"
     err = np.abs(np.asarray(got, LD) - ref)
@@ -137,7 +137,111 @@ def check_columns(got, ref, bound, what=""):
         j = bad[np.argmax((err[bad] / np.maximum(bound[bad], np.finfo(LD).tiny)))]
         raise AssertionError(f"{what}: {bad.size} of {err.size} columns beyond their bound; worst column {j}: "
                              f"got {float(got[j])!r} ref {float(ref[j])!r} err {float(err[j]):.3e} "
-                             f"bound {float(bound[j]):.3e} (K = {K})")
+                             f"bound {float(bound[j]):.3e} (K = {k})")
+
+
+# ---- sparse partitions ----------------------------------------------------------------------------
+# The sparse kernels (csrc/kernels/grad_sparse.hip, eval_sparse.hip) are held to the same bound formula with a
+# constant of their own, measured by the same rule: the plain same-precision scipy path -- CSR ``X.dot(b)``, the
+# residual in the accumulator dtype, ``X.T.dot(r)``, in float64 and in float32 -- over every gradient case of
+# tests/sparse_edge_cases.py (the loop is tests/test_sparse_edge_cases_cpu.py
+# test_measured_sparse_ratio_is_current) reaches at most
+#
+#     MEASURED_SPARSE_CPU_RATIO   (the case, message and column that set it: MEASURED_SPARSE_CPU_CASE)
+#
+# and K_SPARSE = 8 x that, rounded up to a power of two.  What sets it: scipy adds a column's entries one after
+# the other, and a pattern-only column whose rows hold one or two entries carries the same |r| thousands of times
+# (z takes one or two values), so the roundings of the running sum share a sign and the error grows with the
+# column's length (41.4 and 21.2 at the 4096-entry column of the multitile cases, 26.0 at the 924-entry one of
+# the columns cases, 14.8 at ragged d = 1); valued cases stay below 3.7, every case of 5 or more entries per row
+# below 1.9.  The dense constant K above is untouched.
+# On an MI355X the kernels (tiles summed by lane, scan and tile) stayed within 0.0025 of the K_SPARSE bound,
+# 1.3 u sum ..., on every case (columns-fp32-val-d5000-logistic).
+MEASURED_SPARSE_CPU_RATIO = 41.5
+MEASURED_SPARSE_CPU_CASE = "multitile-fp64-pat-d37-logistic message 0 column 5 (41.42)"
+K_SPARSE = 512
+
+
+def sparse_k_rule(ratio: float) -> int:
+    """8 x the measured ratio, rounded up to a power of two."""
+    return int(2 ** int(np.ceil(np.log2(8.0 * ratio))))
+
+
+def hostile_sparse_partition(rng, n, d, counts, valued, prec):
+    """(scipy CSR [n, d], y [n] float64): row i holds a number of non-zeros drawn from ``counts`` (0 allowed; at most
+    d), in sorted columns without duplicates.  valued: N(0, 1) entries scaled per column by 10**U(-3, 1) and
+    rounded to the accumulator type (what the plan stores); else every entry is exactly 1.0.  Labels +-1."""
+    import scipy.sparse as sps
+
+    assert n * d <= 2 ** 24, "a dense [n, d] key matrix is drawn: keep the case small"
+    counts = np.minimum(np.asarray(counts, dtype=np.int64), d)
+    c = counts[rng.randint(0, len(counts), n)] if n else np.zeros(0, dtype=np.int64)
+    order = np.argsort(rng.uniform(size=(n, d)), axis=1)  # a random permutation of the columns per row
+    cols = np.sort(np.where(np.arange(d)[None, :] < c[:, None], order, d), axis=1)  # the first c of it, sorted
+    cols = cols[cols < d].astype(np.int32)
+    indptr = np.concatenate([[0], np.cumsum(c)]).astype(np.int64)
+    if valued:
+        scale = 10.0 ** rng.uniform(-3.0, 1.0, d)
+        npacc = np.float64 if prec.acc == torch.float64 else np.float32
+        data = (rng.randn(cols.size) * scale[cols]).astype(npacc).astype(np.float64)
+    else:
+        data = np.ones(cols.size)
+    y = rng.choice([-1.0, 1.0], n)
+    return sps.csr_matrix((data, cols, indptr), shape=(n, d)), y
+
+
+def hostile_sparse_beta(rng, d, prec, mean_nnz):
+    """hostile_beta for rows of ``mean_nnz`` entries on average: randn(d) 10**U(-2, 0.5, d) 30 / sqrt(max(1, mean_nnz)),
+    so a large share of the margins saturate whatever the rows' length."""
+    b = rng.randn(d) * 10.0 ** rng.uniform(-2.0, 0.5, d) * 30.0 / np.sqrt(max(1.0, mean_nnz))
+    beta = torch.zeros(prec.ld(d), dtype=prec.acc)
+    beta[:d] = torch.from_numpy(b).to(prec.acc)
+    return beta, beta[:d].double().numpy()
+
+
+def oracle_sparse_segment(loss, A, yh, bh, coef):
+    """oracle_segment from the COO triplets of a scipy matrix: (gradient [d], K-free bound sum [d], sum_i |x_ij| [d],
+    z [n]) in long double."""
+    C = A.tocoo()
+    n, d = C.shape
+    rows, cols, x = C.row, C.col, np.asarray(C.data, LD)
+    b = np.asarray(bh, LD)
+    xb = x * b[cols]
+    z, az = np.zeros(n, LD), np.zeros(n, LD)
+    np.add.at(z, rows, xb)
+    np.add.at(az, rows, np.abs(xb))
+    r = oracle_residual(loss, z, yh, coef)
+    w = np.abs(r) + LD(lipschitz(loss, coef)) * az
+    g, acc, ax = np.zeros(d, LD), np.zeros(d, LD), np.zeros(d, LD)
+    np.add.at(g, cols, x * r[rows])
+    np.add.at(acc, cols, np.abs(x) * w[rows])
+    np.add.at(ax, cols, np.abs(x))
+    return g, acc, ax, z
+
+
+def oracle_sparse_terms(loss, segments, host, bh):
+    """(gradient, sum_p sum_i (|r_i| + L_p sum_k |x_ik beta_k|) |x_ij|, sum_p |c_p| sum_i |x_ij|) of one message over
+    scipy partitions: segments = [(partition, coef)], host[p] = (CSR, y)."""
+    d = len(bh)
+    g, acc, tiny = np.zeros(d, LD), np.zeros(d, LD), np.zeros(d, LD)
+    for p, coef in segments:
+        gs, ws, ax, _ = oracle_sparse_segment(loss, host[p][0], host[p][1], bh, coef)
+        g += gs
+        acc += ws
+        tiny += abs(coef) * ax
+    return g, acc, tiny
+
+
+def sparse_bound(acc, tiny, prec, k=None):
+    k = K_SPARSE if k is None else k
+    return LD(k * acc_eps(prec)) * acc + LD(acc_tiny(prec)) * tiny
+
+
+def oracle_sparse_message(loss, segments, host, bh, prec, k=None):
+    """oracle_message over scipy partitions.  A column no partition of the message has an entry in, and every
+    column of a message of coefficient 0, has bound 0: the result must be exactly 0 there."""
+    g, acc, tiny = oracle_sparse_terms(loss, segments, host, bh)
+    return g, sparse_bound(acc, tiny, prec, k)
 
 
 # ---- evaluation GEMM ------------------------------------------------------------------------------
