@@ -1,11 +1,15 @@
 // The one text of the several-scalar-loss-models gradient kernel, compiled once per translation unit that includes
 // it, under the name and with the label rule that unit sets before the #include:
 //
-//   EH_MODELS_KERNEL   the kernel's name (grad_multimodel.hip: grad_models, grad_ovr.hip: grad_ovr)
+//   EH_MODELS_KERNEL   the kernel's name (grad_multimodel.hip: grad_models, grad_ovr.hip: grad_ovr,
+//                      grad_folds.hip: grad_folds)
 //   EH_MODELS_OVR      false: every model sees the rows' own labels (an (alpha, lr) sweep);
 //                      true:  one-vs-rest, labels are class indices and model k sees +1 where the index is k, else -1
+//   EH_MODELS_FOLDS    (optional, default false) true: K-fold cross-validation with K = M, row i of a partition
+//                      belongs to fold i mod M and model k does not see the rows of fold k (their residual is 0)
 //
-// One copy of the row loop; EH_MODELS_OVR changes the one line that picks the label.  The text is included, not
+// One copy of the row loop; EH_MODELS_OVR changes the one line that picks the label, EH_MODELS_FOLDS adds the one
+// line that drops a held-out row's residual (and the scalar fold counter that line reads).  The text is included, not
 // called: moved into a __device__ __forceinline__ template, the same statements compile to the same opcodes in another
 // operand order and register assignment in every grad_models instance (tools/isa_diff.py, docs/PERF_NOTES.md), and
 // the existing kernels' instruction streams are not to move.  No include guard: one kernel per inclusion.
@@ -23,6 +27,9 @@
 // the padding columns [d_x, ld) of every model block.
 #if !defined(EH_MODELS_KERNEL) || !defined(EH_MODELS_OVR)
 #error "define EH_MODELS_KERNEL (the kernel's name) and EH_MODELS_OVR (true / false) before including grad_models_kernel.h"
+#endif
+#ifndef EH_MODELS_FOLDS
+#define EH_MODELS_FOLDS false
 #endif
 
 #include "common.h"
@@ -98,6 +105,17 @@ EH_MODELS_KERNEL(const Segment* __restrict__ segs, const Task* __restrict__ task
 #pragma unroll
     for (int v = 0; v < VN; ++v) gA[j][v] = gB[j][v] = A(0);
 
+  // cross-validation: the fold of a row is its index in the PARTITION (the segment) mod M, whatever task and stage it
+  // falls into.  Wave-uniform and division-free in the loops: fs = fold of the stage's first row, advanced by
+  // srows mod M per stage; a wave's rows start at fs + sub and step by wpg (all reduced mod M once, up here).
+  [[maybe_unused]] int fs = 0, fstage = 0, fsub = 0, fstep = 0;
+  if constexpr (EH_MODELS_FOLDS) {
+    fs = task.row_begin % M;
+    fstage = srows % M;
+    fsub = sub % M;
+    fstep = wpg % M;
+  }
+
   if (nst > 0) issue(0);
   for (int t = 0; t < nst; ++t) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of stage t landed
@@ -108,6 +126,13 @@ EH_MODELS_KERNEL(const Segment* __restrict__ segs, const Task* __restrict__ task
     const A* lab = reinterpret_cast<const A*>(buf + data_bytes);
     const int ns = min(srows, nrows - t * srows);
     const bool hi = lane >= 32;
+    [[maybe_unused]] int f = 0;  // the fold of row i of this stage
+    if constexpr (EH_MODELS_FOLDS) {
+      f = fs + fsub;
+      f -= f >= M ? M : 0;
+      fs += fstage;
+      fs -= fs >= M ? M : 0;
+    }
     for (int i = sub; i < ns; i += wpg) {
       const unsigned char* row = buf + i * rowbytes;
       Rw xr[NV];  // the row, read once: the dot products and the gradient FMAs both use it
@@ -128,7 +153,13 @@ EH_MODELS_KERNEL(const Segment* __restrict__ segs, const Task* __restrict__ task
       A yk = lab[i];
       // one-vs-rest: the label model mA / mB sees is +1 for the rows of its own class and -1 for the others
       if constexpr (EH_MODELS_OVR) yk = yk == static_cast<A>(hi ? mB : mA) ? A(1) : A(-1);
-      const A r = residual<LOSS, A>(zs, yk, A(1));
+      A r = residual<LOSS, A>(zs, yk, A(1));
+      // cross-validation: model mA / mB does not train on the rows of its own fold (the row still feeds the FMAs, with 0)
+      if constexpr (EH_MODELS_FOLDS) {
+        r = f == (hi ? mB : mA) ? A(0) : r;
+        f += fstep;
+        f -= f >= M ? M : 0;
+      }
       const A ra = readlane_a(r, 0), rb = readlane_a(r, 32);  // an idle mB accumulates into gB, never written
 #pragma unroll
       for (int j = 0; j < NV; ++j) {

@@ -182,6 +182,12 @@ hipError_t grad_models_launch(int dtype, int loss, int models, const void* segs,
 hipError_t grad_ovr_launch(int dtype, int loss, int classes, const void* segs, const void* tasks, int ntasks,
                            const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb, int d_x,
                            int ld_x, hipStream_t st, const int* gate = nullptr);
+// K-fold cross-validation (grad_folds.hip): `folds` models of one scalar loss, row i of a partition belongs to fold
+// i mod folds and Gb[p] block k = gradient at beta block k over the rows of partition p whose fold is not k.  dtype
+// and loss as for grad_models_launch.
+hipError_t grad_folds_launch(int dtype, int loss, int folds, const void* segs, const void* tasks, int ntasks,
+                             const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb, int d_x,
+                             int ld_x, hipStream_t st, const int* gate = nullptr);
 
 // layout probes of the bf16 MFMA gradient (grad_mfma.hip): one 16x16x32 product; one transposing read
 hipError_t mfma_probe_launch(const float* A, const float* B, float* C, hipStream_t st);

@@ -71,7 +71,8 @@ std::shared_ptr<GradLauncher> make_dense(int64_t dtype, int64_t loss, int64_t cp
 // rows of blocks * ld_x elements; the plan's device encoding (set_encode) forms the messages unless they are exactly
 // the partitions.  kind 3: softmax, blocks = classes (ops/softmax.py); kind 4: `blocks` independent models of the
 // scalar loss `loss` (ops/multimodel.py); kind 5: one-vs-rest, blocks = classes of the scalar loss `loss`
-// (ops/ovr.py).  who / what: the prefix and the block noun of the error texts.
+// (ops/ovr.py); kind 6: K-fold cross-validation, blocks = fold models of the scalar loss `loss` (ops/cv.py).
+// who / what: the prefix and the block noun of the error texts.
 std::shared_ptr<GradLauncher> make_blocked(int kind, const std::string& who, const std::string& what, int64_t dtype,
                                            int64_t loss, int64_t blocks, const Tensor& segs, const Tensor& tasks,
                                            const Tensor& slab, const Tensor& part_task_begin, int64_t d_x,
@@ -141,6 +142,15 @@ std::shared_ptr<GradLauncher> make_ovr(int64_t dtype, int64_t loss, int64_t clas
   need(dtype == 0 || dtype == 1 || dtype == 3, "one-vs-rest: fp64, fp32 or fp32x64 (fp32 storage, fp64 accumulators)");
   need(loss == 0 || loss == 2, "one-vs-rest: logistic or squared hinge");
   return make_blocked(5, "one-vs-rest", "classes", dtype, loss, classes, segs, tasks, slab, part_task_begin, d_x, ld_x);
+}
+
+std::shared_ptr<GradLauncher> make_folds(int64_t dtype, int64_t loss, int64_t folds, const Tensor& segs,
+                                         const Tensor& tasks, const Tensor& slab, const Tensor& part_task_begin,
+                                         int64_t d_x, int64_t ld_x) {
+  need(dtype == 0 || dtype == 1 || dtype == 3,
+       "cross-validation: fp64, fp32 or fp32x64 (fp32 storage, fp64 accumulators)");
+  need(loss >= 0 && loss <= 2, "cross-validation: logistic, least squares or squared hinge");
+  return make_blocked(6, "cross-validation", "folds", dtype, loss, folds, segs, tasks, slab, part_task_begin, d_x, ld_x);
 }
 
 // Sparse plan (ops/grad.py SparseGradPlan): every distinct local partition once; the plan's device
@@ -337,6 +347,8 @@ void bind_grad_launcher(py::module& m) {
       .def_static("multimodel", &make_multimodel, py::arg("dtype"), py::arg("loss"), py::arg("models"), py::arg("segs"),
                   py::arg("tasks"), py::arg("slab"), py::arg("part_task_begin"), py::arg("d_x"), py::arg("ld_x"))
       .def_static("ovr", &make_ovr, py::arg("dtype"), py::arg("loss"), py::arg("classes"), py::arg("segs"),
+                  py::arg("tasks"), py::arg("slab"), py::arg("part_task_begin"), py::arg("d_x"), py::arg("ld_x"))
+      .def_static("folds", &make_folds, py::arg("dtype"), py::arg("loss"), py::arg("folds"), py::arg("segs"),
                   py::arg("tasks"), py::arg("slab"), py::arg("part_task_begin"), py::arg("d_x"), py::arg("ld_x"))
       .def_static("sparse", &make_sparse, py::arg("loss"), py::arg("y"), py::arg("u"), py::arg("ell_idx"), py::arg("lo"),
                   py::arg("row_ptr"), py::arg("col_idx"), py::arg("vals"), py::arg("crow"), py::arg("cvals"),

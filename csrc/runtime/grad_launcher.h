@@ -15,7 +15,8 @@
 namespace eh {
 
 struct GradLauncher {
-  // 0 dense fused, 1 dense two-pass, 2 sparse, 3 multi-class softmax, 4 several scalar-loss models, 5 one-vs-rest
+  // 0 dense fused, 1 dense two-pass, 2 sparse, 3 multi-class softmax, 4 several scalar-loss models, 5 one-vs-rest,
+  // 6 K-fold cross-validation
   int kind = 0;
   int dtype = 0, loss = 0, cpl = 0, ntasks = 0, nslots = 0, ld = 0;
   KernelChoice choice{};
@@ -29,8 +30,8 @@ struct GradLauncher {
   int acc = 0;
   int rows = 0;   // rows of G a launch writes: nslots, enc_slots after set_encode, the shared message rows (sparse dst)
   SparseArgs sa{};  // kind 2 (grad_sparse.hip); Gb is the launch's output
-  // kind 3 / 4 / 5 (grad_softmax.hip: blocks are classes; grad_multimodel.hip: models of the scalar loss `loss`;
-  // grad_ovr.hip: one-vs-rest classes of the scalar loss `loss`):
+  // kind 3 / 4 / 5 / 6 (grad_softmax.hip: blocks are classes; grad_multimodel.hip: models of the scalar loss `loss`;
+  // grad_ovr.hip: one-vs-rest classes of the scalar loss `loss`; grad_folds.hip: fold models of the scalar loss `loss`):
   // blocks, data columns / row stride of a block (ld is the flattened blocks * ld_x), distinct partitions (the
   // rows the kernel writes) and their task ranges stb [nparts + 1]
   int blocks = 0, d_x = 0, ld_x = 0, nparts = 0;
@@ -111,6 +112,9 @@ struct GradLauncher {
       case 5:
         return grad_ovr_launch(dtype, loss, blocks, segs, tasks, ntasks, stb, nparts, beta, slab, G, d_x, ld_x, st,
                                gate);
+      case 6:
+        return grad_folds_launch(dtype, loss, blocks, segs, tasks, ntasks, stb, nparts, beta, slab, G, d_x, ld_x, st,
+                                 gate);
       default:
         return hipErrorInvalidValue;
     }

@@ -38,6 +38,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--loss logistic | squared_hinge: one-vs-rest over C classes, 2..8: C binary models (class k "
                         "against the rest) from one pass over X per round; labels are class indices 0..C-1, "
                         "prediction is the largest score")
+    g.add_argument("--cv", type=int, default=None, metavar="K",
+                   help="K-fold cross-validation, K in 2..8: K models of the run's scalar loss from one pass over X per "
+                        "round, model k trained without fold k (row i of a partition belongs to fold i mod K); the "
+                        "evaluation reports the mean held-out loss and its spread over the folds")
     g.add_argument("--num-itrs", type=int, default=100)
     g.add_argument("--lr", type=float, default=10.0)
     g.add_argument("--lr-schedule", default="const", choices=["const", "invscaling", "exponential"],
@@ -154,7 +158,7 @@ def parse(argv: List[str]):
                     integrity=not a.no_integrity, delay_on=a.delay_on, slow_ranks=parse_slow_ranks(a.slow_ranks),
                     dedicated_master=a.dedicated_master, device_records=a.device_records,
                     sweep_alpha=a.alphas, sweep_lr=a.lrs, l1=a.l1, sweep_l1=a.l1s,
-                    class_weight=a.class_weight, sample_weights=a.sample_weights, ovr=a.ovr)
+                    class_weight=a.class_weight, sample_weights=a.sample_weights, ovr=a.ovr, cv=a.cv)
     return cfg, a
 
 

@@ -19,6 +19,7 @@ import numpy as np
 
 SWEEP_MIN_MODELS, SWEEP_MAX_MODELS = 2, 8  # csrc/kernels/launchers.h kMinBlocks / kMaxBlocks
 OVR_MIN_CLASSES, OVR_MAX_CLASSES = 2, 8  # likewise: the classes of a one-vs-rest run are the blocks
+CV_MIN_FOLDS, CV_MAX_FOLDS = 2, 8  # likewise: the fold models of a cross-validation run are the blocks
 
 
 def parse_class_weight(spec):
@@ -67,6 +68,9 @@ class RunConfig:
     # one-vs-rest over C = 2..8 classes with the logistic or the squared-hinge loss (auto: logistic): C binary models,
     # class k against the rest, trained from one pass over X per round (ops/ovr.py); labels are class indices
     ovr: Optional[int] = None
+    # K-fold cross-validation, K = 2..8, of the run's scalar loss: K models that share (alpha, lr, l1), model k trained
+    # without the rows of fold k, from one pass over X per round (ops/cv.py); row i of a partition is in fold i mod K
+    cv: Optional[int] = None
     # (alpha, lr) sweep: M = 2..8 models trained in one run from one pass over X per round (ops/multimodel.py).
     # The lists are zipped; an absent list or one of length 1 is broadcast (absent: the run's alpha / lr).
     sweep_alpha: Optional[List[float]] = None
@@ -155,6 +159,8 @@ class RunConfig:
             raise ValueError("drain must be all, carry or lazy")
         if self.ovr is not None:
             self._check_ovr()
+        if self.cv is not None:
+            self._check_cv()
         if self.loss == "softmax":
             self.classes = 2 if self.classes is None else int(self.classes)
             if not 2 <= self.classes <= 8:
@@ -190,6 +196,28 @@ class RunConfig:
         if self.class_weight is not None or self.sample_weights is not None:
             raise ValueError("--ovr: --class-weight / --sample-weights are not supported (the labels are class "
                              "indices and cannot carry a weight)")
+
+    def _check_cv(self) -> None:
+        """The limits of a cross-validation run that the configuration alone decides, each a ValueError naming --cv."""
+        self.cv = int(self.cv)
+        if not CV_MIN_FOLDS <= self.cv <= CV_MAX_FOLDS:
+            raise ValueError(f"--cv: folds must be in {CV_MIN_FOLDS}..{CV_MAX_FOLDS}, got {self.cv}")
+        if self.loss == "softmax":
+            raise ValueError("--cv: not supported with --loss softmax (the fold models are models of a scalar loss: "
+                             "logistic, least_squares or squared_hinge)")
+        if self.ovr is not None:
+            raise ValueError("--cv: cannot be combined with --ovr (the blocks of the model are the folds)")
+        if self.classes is not None:
+            raise ValueError("--cv: cannot be combined with --classes (a softmax option)")
+        if self.sweep_alpha is not None or self.sweep_lr is not None or self.sweep_l1 is not None:
+            raise ValueError("--cv: cannot be combined with a sweep (--alphas / --lrs / --l1s): the fold models "
+                             "share one (alpha, lr, l1)")
+        if self.class_weight is not None or self.sample_weights is not None:
+            raise ValueError("--cv: --class-weight / --sample-weights are not supported")
+        if self.precision == "bf16":
+            raise ValueError("--cv: bf16 storage is not supported (--precision fp64, fp32 or fp32x64)")
+        if self.is_real and self.data != "synthetic":
+            raise ValueError("--cv: sparse data sources are not supported (dense partitions only)")
 
     def _sweep_lists(self) -> Optional[Tuple[List[float], List[float], List[float]]]:
         """([alpha_k], [lr_k], [l1_k]) of a sweep run, every list broadcast to the M models; None without a list."""

@@ -10,6 +10,14 @@ name carries the prefix ``sqhinge_`` so a run in the same data directory keeps t
 Sweep runs (--alphas / --lrs, M models) are scored per model: the arrays get a trailing model axis [R, M], the
 console prints ``>> Model k: alpha = ..., lr = ...`` before model k's usual iteration lines, and model k's
 result names carry the prefix ``sweep{k}_`` (before ``sqhinge_`` where that applies).
+Cross-validation runs (--cv K, K fold models) are scored per fold model the same way, and by the held-out loss: the
+evaluation cuts every training partition it walks into the folds the kernel used (row i of a partition: fold i mod K),
+model k's loss over the rows of fold k is its held-out loss and its loss over the other rows its training loss;
+``EvalResult.cv_loss_folds`` [R, K] is the mean held-out loss of every fold, ``cv_loss`` [R] their mean over the folds
+and ``cv_std`` [R] their standard deviation (ddof = 1).  The console prints ``>> Fold k: held-out rows = n_k of n``
+(the objective's counts) before fold model k's usual lines and closes with ``>> CV: K folds, held-out loss = ... +- ...
+(final round)``; fold model k's result names carry the prefix ``cv{k}_`` (before ``sqhinge_``) and one more file, named
+like the training-loss file with ``cv_loss`` in its place and no fold prefix, holds ``cv_loss``.
 Softmax runs are scored by cross-entropy and accuracy: the console line carries the accuracy where the
 logistic line has the AUC, ``EvalResult.auc`` (and the ``auc`` result file) hold the accuracy, and the
 result names carry the prefix ``softmax_``.
@@ -28,6 +36,7 @@ ones, and the result names carry the prefix ``weighted_`` (after ``sweep{k}_``, 
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import Dict, Optional
 
@@ -55,6 +64,11 @@ class EvalResult:
     # non-zero data columns of every iterate: [R], sweep [R, M]; softmax and one-vs-rest: all C blocks
     nnz: Optional[np.ndarray] = None
     l1_penalty: Optional[np.ndarray] = None  # l1 * ||beta||_1 of every iterate, shaped like nnz
+    # cross-validation runs (the other arrays [R, K], one column per fold model): the mean held-out loss of every
+    # fold [R, K], its mean over the folds [R] and its standard deviation over the folds (ddof = 1) [R]
+    cv_loss_folds: Optional[np.ndarray] = None
+    cv_loss: Optional[np.ndarray] = None
+    cv_std: Optional[np.ndarray] = None
 
 
 def _nnz_line(l1: float, nnz: int, d: int) -> str:
@@ -67,6 +81,40 @@ def _write_nnz(files: Dict[str, str], nnz, key: str = "nnz") -> None:
     head, tail = files[auc_key].rsplit("auc", 1)
     files[key] = head + "nnz" + tail
     dio.save_vector(np.asarray(nnz, dtype=np.float64), files[key])
+
+
+def _write_cv_loss(files: Dict[str, str], prefix: str, cv_loss) -> None:
+    """The cv_loss result file next to fold model 0's training-loss file (written under ``prefix``): the same
+    directory and prefixes without the fold's own, ``training_loss`` -> ``cv_loss``; a training-loss name that does
+    not say ``training_loss`` gets ``cv_loss_`` in front instead."""
+    folder, name = os.path.split(files[prefix + "training_loss"])
+    name = name[len(prefix):] if name.startswith(prefix) else name
+    head, sep, tail = name.rpartition("training_loss")
+    files["cv_loss"] = os.path.join(folder, head + "cv_loss" + tail if sep else "cv_loss_" + name)
+    dio.save_vector(np.asarray(cv_loss, dtype=np.float64), files["cv_loss"])
+
+
+def _cv_sums(chunks, B, d_x: int, kind: int, K: int, prec):
+    """A cross-validation run's loss sums over whole training partitions: (training sums [R, K], held-out sums
+    [R, K], training rows [K], held-out rows [K]).  Every partition is cut into its folds X[k::K] (the rows the
+    kernel held out of model k: a row's fold is its index in the partition mod K), each as a contiguous copy for the
+    evaluation GEMM; model k's sum over fold k is its held-out sum, the other models' sums add to their training sums."""
+    RK = B.shape[0]
+    train, held = np.zeros((RK // K, K)), np.zeros((RK // K, K))
+    n_held, n = np.zeros(K, dtype=np.int64), 0
+    for X, y in chunks:
+        n += X.shape[0]
+        for k in range(K):
+            Xk, yk = X[k::K].contiguous(), y[k::K].contiguous()
+            if Xk.shape[0] == 0:
+                continue
+            s, m = loss_sums([(Xk, yk)], B, d_x, kind, acc=prec)
+            s = np.asarray(s).reshape(RK // K, K)
+            held[:, k] += s[:, k]
+            s[:, k] = 0.0
+            train += s
+            n_held[k] += m
+    return train, held, n - n_held, n_held
 
 
 def _weights_line(trainer: Trainer) -> str:
@@ -194,11 +242,17 @@ def _evaluate_scalar(trainer: Trainer, res: TrainResult, log, write: bool) -> Ev
         if trainer.scheme.logs_eval_loading and not trainer.source.is_sparse:
             for p in parts:
                 log(">> Loaded %d" % (p + 1))
-    sums, n_train = loss_sums(_train_chunks(trainer, parts, prec, dev), B, d_x, kind, acc=prec)
+    cv = spec.kind == "cv"
+    if cv:  # every fold model's training rows are the partitions' rows outside its fold
+        sums, held, rows_k, held_k = _cv_sums(_train_chunks(trainer, parts, prec, dev), B, d_x, kind, M, prec)
+        n_train = int(rows_k[0] + held_k[0])
+        training_loss = sums / np.maximum(1, rows_k)[None, :]
+    else:
+        sums, n_train = loss_sums(_train_chunks(trainer, parts, prec, dev), B, d_x, kind, acc=prec)
+        training_loss = (np.asarray(sums) / max(1, n_train)).reshape(R, M)
     Xt, yt = trainer.source.test(prec, dev)
     P, tsum = predictions_and_loss(Xt, yt, B, d_x, kind, acc=prec)
     n_test = Xt.shape[0]
-    training_loss = (np.asarray(sums) / max(1, n_train)).reshape(R, M)
     testing_loss = (np.asarray(tsum) / max(1, n_test)).reshape(R, M)
     classify = spec.scoring == "auc"
     # weighted runs: the classes behind the weighted labels (an unweighted AUC, comparable across runs)
@@ -229,13 +283,22 @@ def _evaluate_scalar(trainer: Trainer, res: TrainResult, log, write: bool) -> Ev
                 _write_nnz(files, nnz_k[:, k], prefix + "nnz")
     final = testing_loss[-1] if R else np.zeros(M)
     best = spec.best(final)
+    cv_folds = cv_loss = cv_std = None
+    if cv:
+        cv_folds = held / np.maximum(1, held_k)[None, :]
+        cv_loss, cv_std = cv_folds.mean(axis=1), cv_folds.std(axis=1, ddof=1)
+        if files is not None:
+            _write_cv_loss(files, spec.scalar_models()[0][1], cv_loss)
+        if cfg.verbose and R:
+            log(">> CV: %d folds, held-out loss = %g +- %g (final round)" % (M, cv_loss[-1], cv_std[-1]))
     if cfg.verbose:
         if best is not None:
             log(">> Best model: %d (alpha = %g, lr = %g, final test loss %g)"
                 % (best, spec.sweep_alpha[best], spec.sweep_lr[best], final[best]))
         log(">>> Done")
     return EvalResult(spec.per_model(training_loss), spec.per_model(testing_loss), spec.per_model(auc), n_train,
-                      n_test, files, best, nnz=nnz, l1_penalty=pen)
+                      n_test, files, best, nnz=nnz, l1_penalty=pen, cv_loss_folds=cv_folds, cv_loss=cv_loss,
+                      cv_std=cv_std)
 
 
 def evaluate(trainer: Trainer, res: TrainResult, log=None, write: bool = True) -> EvalResult:

@@ -1,7 +1,8 @@
 """What kind of model a run trains, decided once (ModelSpec), and its update schedule (UpdateSchedule).
 
-Four kinds share the engine: a ``single`` model of a scalar loss, ``softmax`` and one-vs-rest (``ovr``) with one
-block per class, and a ``sweep`` of M (alpha, lr, l1) models of one scalar loss.  Everything the engine keeps
+Five kinds share the engine: a ``single`` model of a scalar loss, ``softmax`` and one-vs-rest (``ovr``) with one
+block per class, a ``sweep`` of M (alpha, lr, l1) models of one scalar loss, and the K fold models of a K-fold
+cross-validation (``cv``) of one scalar loss.  Everything the engine keeps
 (beta, messages, history, checkpoints) is one vector of ``ld`` elements, block-major ``[blocks][ld_x]`` with
 ``ld_x = prec.ld(d_x)`` and the padding columns of every block exactly zero; ``d`` of them are stored per round.
 A single model is one block with ``d = d_x``; the other kinds have ``d = ld = blocks * ld_x``.
@@ -19,6 +20,7 @@ import numpy as np
 
 from ..models.losses import (LEAST_SQUARES, LOGISTIC, LOSS_CHOICES, SOFTMAX, SQUARED_HINGE, UpdateRule, base_kind,
                              check_classes, is_classification, weighted_kind)
+from ..ops.cv import CvGradPlan
 from ..ops.grad import DenseGradPlan, SharedGradPlan, SparseGradPlan
 from ..ops.multimodel import MultiModelGradPlan
 from ..ops.ovr import OvrGradPlan
@@ -36,13 +38,17 @@ def sweep_prefix(k: int) -> str:
     return f"sweep{k}_"
 
 
+def cv_prefix(k: int) -> str:
+    return f"cv{k}_"  # result files of fold model k of a cross-validation run (before sqhinge_)
+
+
 @dataclass(frozen=True)
 class ModelSpec:
-    kind: str  # "single" | "softmax" | "ovr" | "sweep"
+    kind: str  # "single" | "softmax" | "ovr" | "sweep" | "cv"
     loss: int  # models/losses.py code, the weighted code of a weighted run; one-vs-rest: the binary loss
     weighted: bool  # class / sample weights: the labels carry them (data/source.py WeightedSource)
     classes: int  # softmax, one-vs-rest: the class blocks; 1 otherwise
-    models: int  # sweep: its models; 1 otherwise
+    models: int  # sweep: its models; cv: its folds; 1 otherwise
     d_x: int  # the data's columns
     ld_x: int  # ... and row stride: one block of the model
     l1: float
@@ -51,6 +57,11 @@ class ModelSpec:
     sweep_l1: Optional[List[float]]
     prec: Precision
     sparse: bool
+    # cross-validation: K, the rows of every fold n_k = sum_p ceil((n_p - k) / K) over the run's partitions, and the
+    # row count n of the run's gradient scale; 0 / None / 0 without --cv
+    cv: int = 0
+    fold_rows: Optional[Tuple[int, ...]] = None
+    n_rows: int = 0
 
     # ---------------------------------------------------------------- resolution and rejections
     @classmethod
@@ -65,6 +76,8 @@ class ModelSpec:
             loss = LOSS_CHOICES[cfg.loss]
         # without weights the run takes exactly the code paths it takes without the feature
         weighted = bool(cfg.weighted or own_weights)
+        if weighted and cfg.cv is not None:  # (a source that brings sample weights of its own; the flags are the
+            raise ValueError("--cv: class / sample weights are not supported")  # config's to reject)
         if weighted:
             if loss not in (LOGISTIC, SQUARED_HINGE):
                 name = {LEAST_SQUARES: "least squares", SOFTMAX: "softmax"}.get(loss, str(loss))
@@ -85,17 +98,43 @@ class ModelSpec:
         sweep = cfg.sweep()
         if sweep:
             kind = "sweep"
+        models, cv = (len(sweep) if sweep else 1), {}
+        if cfg.cv is not None:
+            kind, models = "cv", int(cfg.cv)
+            # the fold counts, and with them n / (n - n_k), assume what the scheme does: equal partitions that add up
+            # to n_rows (check_partitions holds the loaded partitions to it)
+            if int(scheme.n_partition_files) * int(scheme.rows_per_partition) != int(cfg.n_rows):
+                raise ValueError(f"--cv: n_rows = {cfg.n_rows} is not {scheme.n_partition_files} partitions of equal "
+                                 f"size; the fold counts need n_rows to be a multiple of the partition count")
+            per_part = CvGradPlan.fold_rows(scheme.rows_per_partition, models)
+            cv = dict(cv=models, fold_rows=tuple(int(scheme.n_partition_files) * f for f in per_part),
+                      n_rows=int(cfg.n_rows))
+            if max(cv["fold_rows"]) >= cv["n_rows"]:
+                raise ValueError(f"--cv: a fold holds every row ({cv['fold_rows']} of {cv['n_rows']}): its model "
+                                 f"would have nothing to train on")
         d_x = int(cfg.n_cols)
-        spec = cls(kind, loss, weighted, classes, len(sweep) if sweep else 1, d_x, prec.ld(d_x), float(cfg.l1),
+        spec = cls(kind, loss, weighted, classes, models, d_x, prec.ld(d_x), float(cfg.l1),
                    [a for a, _ in sweep] if sweep else None, [x for _, x in sweep] if sweep else None,
-                   cfg.sweep_l1s(), prec, bool(sparse))
+                   cfg.sweep_l1s(), prec, bool(sparse), **cv)
         if kind == "softmax":
             SoftmaxGradPlan.check_supported(prec, classes, sparse)
         elif kind == "ovr":
             OvrGradPlan.check_supported(prec, loss, classes, sparse, spec.ld_x, gpu)
         elif kind == "sweep":
             MultiModelGradPlan.check_supported(prec, loss, spec.models, sparse, spec.ld_x, gpu)
+        elif kind == "cv":
+            CvGradPlan.check_supported(prec, loss, spec.models, sparse, spec.ld_x, gpu)
         return spec
+
+    def check_partitions(self, parts, rows_per_partition: int) -> None:
+        """A cross-validation run's loaded partitions {p: (X, y)} must have the scheme's rows each: fold_rows, and the
+        scale of every fold model's gradient, are counted from that size.  Any other run: nothing to check."""
+        if self.kind != "cv":
+            return
+        for p, (X, _) in sorted(parts.items()):
+            if int(X.shape[0]) != int(rows_per_partition):
+                raise ValueError(f"--cv: partition {p} has {X.shape[0]} rows, the scheme's partitions have "
+                                 f"{rows_per_partition}: the fold counts n_k (and n / (n - n_k)) assume equal partitions")
 
     # ------------------------------------------------------------------------------- the layout
     @property
@@ -115,6 +154,20 @@ class ModelSpec:
     @property
     def ovr(self) -> bool:
         return self.kind == "ovr"
+
+    @property
+    def per_model_scores(self) -> bool:
+        """The run's scores carry a trailing model axis: the models of a sweep, the fold models of a cross-validation."""
+        return self.kind in ("sweep", "cv")
+
+    @property
+    def cv_scale(self) -> Optional[np.ndarray]:
+        """[K] n / (n - n_k): fold model k's mean is over the rows it trains on, so its gradient multiplier is the
+        single model's times this; None without --cv."""
+        if self.kind != "cv":
+            return None
+        n = float(self.n_rows)
+        return np.array([n / (n - f) for f in self.fold_rows], dtype=np.float64)
 
     @property
     def blocked(self) -> bool:
@@ -158,7 +211,7 @@ class ModelSpec:
     def beta0(self, init_zero: bool, seed: Optional[int]) -> np.ndarray:
         """beta_0 packed [ld]: randn (naive/replication/approx) or zeros (ref §2.2 'Per-scheme beta init').  Softmax
         and one-vs-rest draw classes * d_x values in one call; every model of a sweep starts from the single-model
-        run's beta_0."""
+        run's beta_0, and so does every fold model of a cross-validation."""
         nb = self.classes * self.d_x
         if init_zero:
             b0 = np.zeros(nb)
@@ -175,6 +228,8 @@ class ModelSpec:
         blocks = self.unpack(np.asarray(betaset, dtype=np.float64))
         if self.kind == "sweep":
             return np.count_nonzero(blocks, axis=2), np.abs(blocks).sum(axis=2) * np.asarray(self.sweep_l1, np.float64)
+        if self.kind == "cv":  # [R, K]: every fold model with the run's one lambda
+            return np.count_nonzero(blocks, axis=2), np.abs(blocks).sum(axis=2) * self.l1
         flat = blocks.reshape(blocks.shape[0], -1)
         return np.count_nonzero(flat, axis=1), np.abs(flat).sum(axis=1) * self.l1
 
@@ -187,6 +242,8 @@ class ModelSpec:
             return OvrGradPlan(messages, parts, self.prec, self.loss, self.classes, self.d_x)
         if self.kind == "sweep":
             return MultiModelGradPlan(messages, parts, self.prec, self.loss, self.models, self.d_x)
+        if self.kind == "cv":
+            return CvGradPlan(messages, parts, self.prec, self.loss, self.models, self.d_x)
 
         def one(msgs):
             if self.sparse:
@@ -214,6 +271,9 @@ class ModelSpec:
     def scalar_models(self) -> List[Tuple[Optional[str], str, float]]:
         """(console header, result prefix, l1) of every model a scalar-loss run scores: a single model has no
         header and no prefix of its own."""
+        if self.kind == "cv":  # n_k of n: the rows fold model k does not train on, of the objective's row count
+            return [(">> Fold %d: held-out rows = %d of %d" % (k, self.fold_rows[k], self.n_rows), cv_prefix(k), self.l1)
+                    for k in range(self.models)]
         if self.kind != "sweep":
             return [(None, "", self.l1)]
         return [(">> Model %d: alpha = %g, lr = %g" % (k, self.sweep_alpha[k], self.sweep_lr[k])
@@ -221,8 +281,8 @@ class ModelSpec:
                 for k in range(self.models)]
 
     def per_model(self, a: np.ndarray) -> np.ndarray:
-        """[R, M] scores as the run reports them: a trailing model axis only in a sweep."""
-        return a if self.kind == "sweep" else a[:, 0]
+        """[R, M] scores as the run reports them: a trailing model axis only in a sweep or a cross-validation."""
+        return a if self.per_model_scores else a[:, 0]
 
     def best(self, final: np.ndarray) -> Optional[int]:
         """A sweep's model with the lowest final test loss [M] (non-finite ones last); None otherwise."""
@@ -231,8 +291,8 @@ class ModelSpec:
         return int(np.argmin(np.where(np.isfinite(final), final, np.inf)))
 
     def result_names(self, names: Dict[str, str], model_prefix: str = "") -> Dict[str, str]:
-        """The scheme's result names under the run's prefixes: ``sweep{k}_`` first, then ``softmax_`` / ``ovr_``,
-        ``weighted_``, ``sqhinge_``."""
+        """The scheme's result names under the run's prefixes: ``sweep{k}_`` / ``cv{k}_`` first, then ``softmax_`` /
+        ``ovr_``, ``weighted_``, ``sqhinge_``."""
         p = model_prefix + {"softmax": SOFTMAX_PREFIX, "ovr": OVR_PREFIX}.get(self.kind, "")
         p += (WEIGHTED_PREFIX if self.weighted else "") + (SQHINGE_PREFIX if base_kind(self.loss) == SQUARED_HINGE else "")
         return {k: p + v for k, v in names.items()}
@@ -245,6 +305,8 @@ class ModelSpec:
             rep.update(models=self.models, sweep_alpha=list(self.sweep_alpha), sweep_lr=list(self.sweep_lr))
         if self.kind == "ovr":
             rep.update(ovr=True, classes=self.classes)
+        if self.kind == "cv":
+            rep.update(cv=self.cv, fold_rows=list(self.fold_rows))
         rep.update(l1=list(self.sweep_l1) if self.kind == "sweep" else self.l1, prox=bool(self.prox),
                    weighted=bool(self.weighted))
         return rep
@@ -261,6 +323,8 @@ class ModelSpec:
             state["weights"] = weight_spec
         if self.kind == "ovr":
             state["ovr"] = int(self.classes)
+        if self.kind == "cv":
+            state["cv"] = int(self.cv)
         return state
 
     def check_checkpoint(self, st, path: str, weight_spec) -> None:
@@ -285,6 +349,10 @@ class ModelSpec:
         if have_ovr != want_ovr:
             raise ValueError(f"checkpoint {path} was written by a run with ovr = {have_ovr}; this run has "
                              f"ovr = {want_ovr} (--ovr)")
+        have_cv, want_cv = st.get("cv"), (self.cv if self.kind == "cv" else None)
+        if have_cv != want_cv:
+            raise ValueError(f"checkpoint {path} was written by a run with cv = {have_cv}; this run has "
+                             f"cv = {want_cv} (--cv)")
         have_w = st.get("weights")
         if have_w != weight_spec:
             raise ValueError(f"checkpoint {path} was written by a run with weights = {have_w}; this run has "
@@ -296,7 +364,7 @@ class ModelSpec:
 @dataclass
 class UpdateSchedule:
     """Every round's update coefficients, filled once per run from the UpdateRule (models/losses.py): B = the
-    models of a sweep, 1 otherwise."""
+    models of a sweep or the fold models of a cross-validation, 1 otherwise."""
 
     decay: np.ndarray  # [R, B]
     gm: np.ndarray  # [R, B]
@@ -321,6 +389,10 @@ class UpdateSchedule:
             B, block = spec.models, (spec.ld_x, spec.d_x)
             bco = [rule.block_coeffs(i, sweep_etas[:, i], spec.sweep_alpha) for i in range(R)]
             decay, gm, l2 = (np.array([c[k] for c in bco], dtype=np.float64).reshape(R, B) for k in range(3))
+        elif spec.kind == "cv":  # every fold model takes the single-model coefficients; gm times n / (n - n_k)
+            B, block = spec.models, (spec.ld_x, spec.d_x)
+            decay, gm, l2 = (np.repeat(single[k].reshape(R, 1), B, axis=1) for k in range(3))
+            gm = gm * spec.cv_scale[None, :]
         else:
             B, block = 1, (spec.ld, spec.d)
             decay, gm, l2 = (single[k].reshape(R, 1) for k in range(3))
@@ -328,7 +400,8 @@ class UpdateSchedule:
         if spec.prox:  # the soft threshold eta_i * l1 (per model in a sweep)
             thr = [rule.block_thresholds(i, sweep_etas[:, i], spec.sweep_l1) if spec.kind == "sweep"
                    else [rule.threshold(i, float(eta[i]))] for i in range(R)]
-            thr = np.array(thr, dtype=np.float64).reshape(R, B)
+            thr = np.array(thr, dtype=np.float64).reshape(R, -1)
+            thr = np.repeat(thr, B, axis=1) if spec.kind == "cv" else thr.reshape(R, B)
         return cls(decay, gm, l2, thr, theta, code, *block, single)
 
     def apply(self, i: int, msgs, coefs, beta, u, hist, beta_w) -> None:

@@ -143,6 +143,7 @@ class Trainer:
     ovr = property(lambda self: self.model.ovr)
     blocked = property(lambda self: self.model.blocked)
     models = property(lambda self: self.model.models)
+    cv = property(lambda self: self.model.cv)
     sweep_alpha = property(lambda self: self.model.sweep_alpha)
     sweep_lr = property(lambda self: self.model.sweep_lr)
     sweep_l1 = property(lambda self: self.model.sweep_l1)
@@ -264,6 +265,7 @@ class Trainer:
         t0 = time.perf_counter()
         parts = {p: source.partition(p, self.prec, dev) for p in needed}
         self.load_seconds = time.perf_counter() - t0
+        self.model.check_partitions(parts, sch.rows_per_partition)
         if self.weighted:
             self._weight_sum(parts)
         self.plan = self.model.make_plan([m.segments for m in self.local_msgs], parts, cfg, dev)

@@ -249,6 +249,22 @@ _GRADS = {LOGISTIC: logistic_grad, LEAST_SQUARES: least_squares_grad, SQUARED_HI
           LOGISTIC_W: logistic_w_grad, SQUARED_HINGE_W: squared_hinge_w_grad}
 
 
+def cv_fold_mask(n: int, folds: int) -> np.ndarray:
+    """[n, K] bool: entry (i, k) is True where row i of a partition trains fold model k, that is where its fold
+    i mod K is not k (the rows model k of a cross-validation run sees)."""
+    return (np.arange(int(n)) % int(folds))[:, None] != np.arange(int(folds))[None, :]
+
+
+def cv_grad(kind: int, X, y: np.ndarray, B: np.ndarray, coef=None) -> np.ndarray:
+    """[K, d]: block k is the scalar-loss gradient at B_k over the rows of the partition (X, y) whose fold is not k."""
+    if kind not in (LOGISTIC, LEAST_SQUARES, SQUARED_HINGE):
+        raise ValueError(f"cross-validation: loss kind {kind} is not logistic, least squares or squared hinge")
+    B = np.asarray(B, dtype=np.float64)
+    keep = cv_fold_mask(X.shape[0], B.shape[0])
+    y = np.asarray(y)
+    return np.stack([_GRADS[kind](X[keep[:, k]], y[keep[:, k]], B[k], coef) for k in range(B.shape[0])])
+
+
 def worker_grad(kind: int, X, y, beta, coef=None) -> np.ndarray:
     if kind == SOFTMAX:  # beta: the flattened [C, X.shape[1]] model; returns the gradient flattened alike
         d = X.shape[1]

@@ -9,7 +9,8 @@
   loss on the same data in the same process, in the order given (repeat names to alternate);
   ``softmax`` among them times the one-pass multi-class kernel for every ``--classes C,...`` and
   ``multimodel`` the one-pass M-model kernel of an (alpha, lr) sweep for every ``--models M,...`` and ``ovr``
-  the one-pass one-vs-rest kernel (logistic) for every ``--classes C,...``;
+  the one-pass one-vs-rest kernel (logistic) for every ``--classes C,...``; ``--cv K,...`` adds the one-pass
+  cross-validation kernel (logistic) for every fold count, to hold against ``multimodel`` at M = K;
 * sparse one-hot gradients on covtype / kc_house / amazon-shaped data (the reference's real
   datasets, synthetic stand-ins of the same shape): the ELL path against the generic
   sorted-COO path.
@@ -136,7 +137,7 @@ def scale_cases(out):
 
 
 def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_000), precs=("fp64", "fp32"),
-                losses=("logistic",), classes=(2,), models=(2,), layouts_only=None, weighted=False):
+                losses=("logistic",), classes=(2,), models=(2,), layouts_only=None, weighted=False, folds=(2,)):
     """Shape sweep of the dense gradient against the device-copy ceiling (round-2 verdict item 6).
 
     For every (precision, d, n): n rows in 8 partitions, two message layouts -- ``naive`` (one
@@ -149,7 +150,9 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
     (rows of at most 1024 columns, fp64 / fp32; other precisions are skipped with a note).  ``multimodel`` runs
     MultiModelGradPlan (logistic) on the same X and labels, once per M of ``models``; ``ms_per_model`` is its time
     over M, to hold against the one-model logistic rows.  ``ovr`` runs OvrGradPlan (logistic) on the same X with labels
-    randint(0, C), once per C of ``classes``; ``ms_per_model`` is its time over C.
+    randint(0, C), once per C of ``classes``; ``ms_per_model`` is its time over C.  ``cv`` runs CvGradPlan (logistic,
+    the cross-validation kernel) on the same X and labels, once per K of ``folds``, to hold against the ``multimodel``
+    row at M = K.
     ``weighted``: the same plans run the weighted code of the loss (logistic, squared_hinge) on labels
     y~ = y * w, w = 10**U(-2, 2) drawn once per partition -- the A/B of class / sample weights against a run without
     the flag.
@@ -159,6 +162,7 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
     from erasurehead_amd.models.losses import LOSS_NAMES, weighted_kind
     from erasurehead_amd.ops import DenseGradPlan, SoftmaxGradPlan, get_precision
     from erasurehead_amd.ops.multimodel import MultiModelGradPlan
+    from erasurehead_amd.ops.cv import CvGradPlan
     from erasurehead_amd.ops.ovr import OvrGradPlan
 
     layouts = {"naive": [[p] for p in range(8)], "agc": [[0, 1, 2]] * 3 + [[3, 4, 5]] * 3 + [[6, 7]] * 2}
@@ -195,6 +199,22 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
                                 r = {"kernel": "grad_models_sweep", "precision": prec_name, "d": d, "n": n,
                                      "layout": lay, "loss": "logistic", "models": M, "tasks": plan.ntasks, "ms": ms,
                                      "ms_per_model": ms / M, "distinct_TBps": distinct / ms * 1e3,
+                                     "copy_TBps": ceiling, "frac": distinct / ms * 1e3 / ceiling}
+                                out.append(r)
+                                print(json.dumps(r), flush=True)
+                                del plan, G
+                            continue
+                        if loss == "cv":
+                            for K in folds:
+                                plan = CvGradPlan([[(p, 1.0) for p in m] for m in msgs], parts, prec,
+                                                  LOSS_NAMES["logistic"], K, d)
+                                bK = torch.randn(plan.ld, device="cuda", dtype=prec.acc) * 0.01
+                                G = plan.out_buffer()[0]
+                                ms = _time(lambda: plan.run(bK, G), reps=20)
+                                distinct = 8 * nbytes / 1e12  # TB
+                                r = {"kernel": "grad_folds_sweep", "precision": prec_name, "d": d, "n": n,
+                                     "layout": lay, "loss": "logistic", "folds": K, "tasks": plan.ntasks, "ms": ms,
+                                     "ms_per_model": ms / K, "distinct_TBps": distinct / ms * 1e3,
                                      "copy_TBps": ceiling, "frac": distinct / ms * 1e3 / ceiling}
                                 out.append(r)
                                 print(json.dumps(r), flush=True)
@@ -403,6 +423,9 @@ def main():
                          "logistic kernel)")
     ap.add_argument("--classes", default="2", help="--only sweep --loss softmax / ovr: class counts, e.g. 2,4,7,8")
     ap.add_argument("--models", default="2", help="--only sweep --loss multimodel: model counts, e.g. 2,4,8")
+    ap.add_argument("--cv", default=None, metavar="K,...",
+                    help="--only sweep: also run the cross-validation kernel (grad_folds) for these fold counts, e.g. "
+                         "2,4,8; with --loss multimodel --models 2,4,8 the sweep kernel at M = K runs next to it")
     ap.add_argument("--weighted", action="store_true",
                     help="--only sweep / sparse: the weighted code of the loss on labels y * w, w = 10**U(-2, 2) (logistic, "
                          "squared_hinge; sparse: logistic) -- compare with a run without the flag")
@@ -434,9 +457,11 @@ def main():
     from erasurehead_amd.models.losses import LOSS_CHOICES
 
     losses = tuple(a.loss.split(","))
-    if any(x not in LOSS_CHOICES and x not in ("multimodel", "ovr") for x in losses):
-        ap.error(f"--loss: names from {sorted(LOSS_CHOICES) + ['multimodel', 'ovr']}")
-    if a.weighted and any(x in ("least_squares", "softmax", "multimodel", "ovr") for x in losses):
+    if a.cv and "cv" not in losses:  # (``cv`` may also be named in --loss, to alternate it with the other kernels)
+        losses += ("cv",)
+    if any(x not in LOSS_CHOICES and x not in ("multimodel", "ovr", "cv") for x in losses):
+        ap.error(f"--loss: names from {sorted(LOSS_CHOICES) + ['multimodel', 'ovr', 'cv']}")
+    if a.weighted and any(x in ("least_squares", "softmax", "multimodel", "ovr", "cv") for x in losses):
         ap.error("--weighted: logistic or squared_hinge (no other kernel has a weighted instance)")
     out = []
     if a.only in (None, "dense"):
@@ -449,7 +474,8 @@ def main():
         sweep_cases(out, ds=tuple(int(x) for x in a.ds.split(",")), ns=tuple(int(float(x)) for x in a.ns.split(",")),
                     precs=tuple(a.precs.split(",")), losses=losses, classes=tuple(int(c) for c in a.classes.split(",")),
                     models=tuple(int(m) for m in a.models.split(",")),
-                    layouts_only=a.sweep_layouts.split(",") if a.sweep_layouts else None, weighted=a.weighted)
+                    layouts_only=a.sweep_layouts.split(",") if a.sweep_layouts else None, weighted=a.weighted,
+                    folds=tuple(int(k) for k in a.cv.split(",")) if a.cv else (2,))
     if a.only == "choices":
         if a.shapes:
             choice_cases(out, [(p, int(d), int(float(n))) for p, d, n in (x.split(":") for x in a.shapes.split(","))],
