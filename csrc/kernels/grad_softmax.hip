@@ -218,4 +218,9 @@ hipError_t grad_softmax_launch(int dtype, int classes, const void* segs, const v
   });
 }
 
+void blocks_geometry(int rowbytes, int blocks, int* stage_rows, int* wpg) {
+  *stage_rows = blocks_stage_rows(rowbytes);
+  *wpg = blocks_wpg(blocks);
+}
+
 }  // namespace eh

@@ -188,6 +188,9 @@ hipError_t grad_ovr_launch(int dtype, int loss, int classes, const void* segs, c
 hipError_t grad_folds_launch(int dtype, int loss, int folds, const void* segs, const void* tasks, int ntasks,
                              const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb, int d_x,
                              int ld_x, hipStream_t st, const int* gate = nullptr);
+// What grad_blocks.h answers for rows of `rowbytes` bytes and a model of `blocks` blocks: blocks_stage_rows and
+// blocks_wpg themselves (the tests hold the Python mirrors in ops/blockplan.py to them).
+void blocks_geometry(int rowbytes, int blocks, int* stage_rows, int* wpg);
 
 // layout probes of the bf16 MFMA gradient (grad_mfma.hip): one 16x16x32 product; one transposing read
 hipError_t mfma_probe_launch(const float* A, const float* B, float* C, hipStream_t st);

@@ -30,6 +30,17 @@ TASKS_PER_CU = 2  # workgroups of 4 waves and <= 67 KiB of LDS: two per CU
 MIN_ROWS_PER_TASK = 64
 
 
+def stage_rows(rowbytes: int) -> int:
+    """Rows per LDS stage: a mirror of csrc/kernels/grad_blocks.h blocks_stage_rows (about 32 KiB, 4..32 rows)."""
+    return min(32, max(4, 32768 // int(rowbytes)))
+
+
+def waves_per_group(blocks: int) -> int:
+    """Waves that share one pair of blocks and split a stage's rows: a mirror of grad_blocks.h blocks_wpg
+    (2 blocks -> 4, 3 or 4 -> 2, 5..8 -> 1)."""
+    return SUBS // ((int(blocks) + 1) // 2)
+
+
 class BlockGradPlan:
     """Gradient of every local message for a model of ``blocks`` blocks over dense partitions.
 

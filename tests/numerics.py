@@ -29,8 +29,21 @@ The evaluation GEMM uses the same scheme: |dP_ij| <= K u sum_k |x_ik b_jk|, and 
 sum_i Lip_i dP_ij + K 2^-52 sum_i loss_i (Lip_i = 1 logistic, 2 |y - p| least squares,
 2 max(0, 1 - y p) squared hinge; the epilogue sums in fp64 with atomics).
 
-The oracle computes in ``np.longdouble`` with scipy's overflow-free expit and shares no code with
-erasurehead_amd.models.losses (only the integer loss codes are the package's).
+Softmax (C classes, model B [C, d], class blocks of one message): every column of every class block is
+held to
+
+    w_ic     = |r_ic| + p_ic + 1/2 max_j sum_k |x_ik B_jk|
+    bound_cj = K u sum_p |c_p| sum_i w_ic |x_ij|  +  C tiny sum_p |c_p| sum_i |x_ij|
+
+|r| is the accumulation of X^T r; p: the true class's p - 1 cancels, so its error is absolute in p;
+1/2 max: the softmax Jacobian's infinity norm is at most 1/2, applied to the dot products' error;
+C tiny: up to C exps flushed to zero per row.  The plain path (SoftmaxGradPlan on CPU tensors, fp64 and
+fp32) reaches MEASURED_SOFTMAX_CPU_RATIO = 0.77 over the cases of tests/block_edge_cases.py, which by the
+same rule gives K = 8 again (the softmax section below has the case and what sets it).
+
+The oracle computes in ``np.longdouble`` with scipy's overflow-free expit (the softmax oracle: the row's
+maximum subtracted before exp) and shares no code with erasurehead_amd.models.losses (only the integer
+loss codes are the package's).
 """
 import numpy as np
 import torch
@@ -242,6 +255,105 @@ def oracle_sparse_message(loss, segments, host, bh, prec, k=None):
     column of a message of coefficient 0, has bound 0: the result must be exactly 0 there."""
     g, acc, tiny = oracle_sparse_terms(loss, segments, host, bh)
     return g, sparse_bound(acc, tiny, prec, k)
+
+
+# ---- softmax (blocked model: C classes) -------------------------------------------------------------
+# The softmax kernel (csrc/kernels/grad_softmax.hip) is held to the bound of the header's softmax paragraph, its
+# constant measured by the same rule: the plain same-precision path is SoftmaxGradPlan on CPU tensors
+# (softmax_grad_torch), in fp64 and fp32, over every case of tests/block_edge_cases.py softmax_cases() and both
+# message sets (the loop is tests/test_block_edge_cases_cpu.py test_measured_softmax_ratio_is_current), and its largest
+# err_cj / (u sum_p |coef_p| sum_i w_ic |x_ij| + C tiny ...) is
+#
+#     MEASURED_SOFTMAX_CPU_RATIO   (the case, message, class and column that set it: MEASURED_SOFTMAX_CPU_CASE)
+#
+# That is just above the dense MEASURED_CPU_RATIO (0.72), so sparse_k_rule applies: 8 x 0.77 rounded up to a power of
+# two is 8 again, K_SOFTMAX = K, and the softmax kernel has no constant of its own.  What sets it: the logits of the
+# offset model, in either precision (fp64 reaches 0.751).  |z| is hundreds there, so a logit carries an absolute error
+# of about u sum_k |x_ik B_ck| into a softmax whose logits differ by O(1) -- the 1/2 max_j sum_k |x_ik B_jk| term of
+# w -- and a 16-row partition has no room to average it out.  The saturated model (residuals of exactly 0 and -1 in
+# most rows) stays below 0.28.
+# On an MI355X the kernel (lane-strided dot products, DPP softmax, per-wave slab rows) stayed within 0.06 of the
+# K_SOFTMAX bound, 0.48 u sum ..., on every case (fp32-d1-C5-offset, naive messages, whole tasks).
+MEASURED_SOFTMAX_CPU_RATIO = 0.77
+MEASURED_SOFTMAX_CPU_CASE = "fp32-d256-C3-offset naive message 4 class 0 (0.763)"
+K_SOFTMAX = 8  # sparse_k_rule(MEASURED_SOFTMAX_CPU_RATIO): the dense K
+
+
+def hostile_class_labels(rng, n, C, prec):
+    """(y [n] accumulator dtype, its float64 NumPy copy): class indices uniform in 0..C-1.  The callers make sure
+    that some partition lacks class C - 1 and that the one-row partition exists."""
+    y = rng.randint(0, C, n).astype(np.float64)
+    return torch.from_numpy(y).to(prec.acc), y
+
+
+def _class_major(blocks, d, prec):
+    ld = prec.ld(d)
+    beta = torch.zeros((len(blocks), ld), dtype=prec.acc)
+    beta[:, :d] = torch.from_numpy(np.stack(blocks)).to(prec.acc)
+    return beta.reshape(-1).contiguous(), beta[:, :d].double().numpy()
+
+
+def hostile_softmax_models(rng, host, d, C, prec):
+    """{"saturated", "offset"}: each (beta [C * ld] accumulator dtype, class-major with zero padding; its fp64 view
+    [C, d]).  host[p] = (fp64 view of X, ...) gives the column scales the offset model is built for.
+
+    saturated: C independent hostile_beta draws -- one class takes probability exactly 1.0 in many rows and the other
+               exps underflow.
+    offset:    B_c = b + delta_c, b one hostile_beta draw (a common logit of hundreds that only the max subtraction
+               removes) and delta_c[j] = 1.5 randn / (sqrt(d) rms_j), rms_j the root mean square of column j over all
+               partitions (1 where that is 0): the logits differ by O(1) while |z| is large."""
+    sat = [hostile_beta(rng, d, prec)[1] for _ in range(C)]
+    b = hostile_beta(rng, d, prec)[1]
+    rows = sum(X.shape[0] for X, *_ in host.values())
+    sq = sum((np.asarray(X, np.float64) ** 2).sum(0) for X, *_ in host.values())
+    rms = np.sqrt(sq / max(1, rows))
+    rms = np.where(rms == 0, 1.0, rms)
+    off = [b + 1.5 * rng.randn(d) / (np.sqrt(d) * rms) for _ in range(C)]
+    return {"saturated": _class_major(sat, d, prec), "offset": _class_major(off, d, prec)}
+
+
+def oracle_softmax_probs(Xh, Bh):
+    """(p [n, C], z [n, C]) in long double, the row's maximum subtracted before the exp."""
+    Z = np.asarray(Xh, LD) @ np.asarray(Bh, LD).T
+    with np.errstate(under="ignore"):
+        E = np.exp(Z - Z.max(axis=1, keepdims=True)) if Z.size else Z
+    return E / np.maximum(E.sum(axis=1, keepdims=True), LD(1)), Z
+
+
+def oracle_softmax_segment(Xh, yh, Bh):
+    """One segment with coefficient 1: (gradient [C, d], K-free bound sum_i w_ic |x_ij| [C, d], sum_i |x_ij| [d]) in
+    long double, w_ic = |r_ic| + p_ic + 1/2 max_j sum_k |x_ik B_jk|."""
+    X, B = np.asarray(Xh, LD), np.asarray(Bh, LD)
+    P, _ = oracle_softmax_probs(X, B)
+    R = P.copy()
+    R[np.arange(X.shape[0]), np.asarray(yh).astype(np.int64)] -= LD(1)
+    aX = np.abs(X)
+    dots = (aX @ np.abs(B).T).max(axis=1, keepdims=True) if X.shape[0] else np.zeros((0, 1), LD)
+    W = np.abs(R) + P + LD(0.5) * dots
+    return R.T @ X, W.T @ aX, aX.sum(0)
+
+
+def oracle_softmax_terms(segments, host, Bh):
+    """(gradient, sum_p |coef_p| sum_i w_ic |x_ij|, sum_p |coef_p| sum_i |x_ij|), [C, d] each, of one message:
+    segments = [(partition, coef)], host[p] = (X, y)."""
+    C, d = np.shape(Bh)
+    g, acc, tiny = np.zeros((C, d), LD), np.zeros((C, d), LD), np.zeros((C, d), LD)
+    for p, coef in segments:
+        gs, ws, ax = oracle_softmax_segment(host[p][0], host[p][1], Bh)
+        g += LD(coef) * gs
+        acc += LD(abs(coef)) * ws
+        tiny += LD(abs(coef)) * ax[None, :]
+    return g, acc, tiny
+
+
+def softmax_bound(acc, tiny, C, prec, k=K_SOFTMAX):
+    return LD(k * acc_eps(prec)) * acc + LD(C * acc_tiny(prec)) * tiny
+
+
+def oracle_softmax_message(segments, host, Bh, prec, k=K_SOFTMAX):
+    """(gradient [C, d], per-class, per-column bound [C, d]) of one softmax message."""
+    g, acc, tiny = oracle_softmax_terms(segments, host, Bh)
+    return g, softmax_bound(acc, tiny, np.shape(Bh)[0], prec, k)
 
 
 # ---- evaluation GEMM ------------------------------------------------------------------------------

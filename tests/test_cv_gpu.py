@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 import torch
 
+import block_edge_cases as bc
 from cv_cases import CASES, TOL, check_against_replay, make
 from erasurehead_amd.engine import Trainer, evaluate
 from erasurehead_amd.models import losses
@@ -106,6 +107,53 @@ def test_kernel_within_the_column_bounds(d, loss, prec_name, K, native):
         torch.cuda.synchronize()
         check(G, msgs, host, bhs, loss, prec, d, f"{'naive' if msgs is NAIVE else 'coded'} K={K}")
         assert torch.equal(G, G2)  # two launches: bitwise identical
+
+
+# ---- 1b. stage edges: ragged stages of every row count, ring reuse, tasks that start at odd rows
+STAGE_GRID = bc.scalar_grid(LOSSES)
+_edge_parts = {}
+
+
+@pytest.mark.parametrize("K", bc.SCALAR_BLOCKS)
+@pytest.mark.parametrize("d,loss,prec_name", STAGE_GRID, ids=[f"d{d}-{LOSS_IDS[l]}-{p}" for d, l, p in STAGE_GRID])
+def test_stage_edges_within_the_column_bounds(d, loss, prec_name, K, native, monkeypatch):
+    """Partitions of tests/block_edge_cases.py partition_sizes (every ragged stage around a row per wave and the full
+    stage, S + 1, 2S, 2S + 1, 3S + 2, empty), once as whole tasks of three and four stages and once cut into tasks of
+    37 rows, naive and coded messages; the same oracle, bound and checks as above.  Tasks that start at rows 37 and
+    74 are the point here: the fold of a row is its index in the partition mod K, so under tasks of 37 rows block k
+    must still be bitwise the sweep kernel's block k on the data with the rows of fold k zeroed."""
+    prec = get_precision(prec_name)
+    sizes, cpu_parts, host, betas = bc.scalar_inputs(d, prec_name, K)
+    if (d, prec_name, K) not in _edge_parts:
+        _edge_parts[(d, prec_name, K)] = bc.to_device(cpu_parts, DEV)
+    parts = _edge_parts[(d, prec_name, K)]
+    beta, bhs = model(betas, K)
+    ld = prec.ld(d)
+    for rows in bc.TASK_ROWS:
+        bc.forced_task_rows(monkeypatch, rows)
+        for kind in ("naive", "coded"):
+            msgs = bc.MESSAGES[kind](len(sizes))
+            plan = CvGradPlan(msgs, parts, prec, loss, K, d)
+            assert plan.identity == (kind == "naive")
+            bc.assert_tasks_reach_the_edges(plan, sizes, bc.geometry(prec, d, K)[0], rows)
+            G = plan.out_buffer()[0].fill_(float("nan"))
+            plan.run(beta, G)
+            G2 = plan.out_buffer()[0].fill_(float("nan"))
+            plan.native_launcher().launch(beta, G2)
+            torch.cuda.synchronize()
+            check(G, msgs, host, bhs, loss, prec, d, f"{kind} K={K} tasks of {rows}")
+            assert torch.equal(G, G2)  # two launches: bitwise identical
+        if rows == bc.ODD_TASKS:  # G: the coded messages
+            for k in range(K):
+                parts_k = {}
+                for p, (X, y) in parts.items():
+                    Xk = X.clone()
+                    Xk[k::K] = 0
+                    parts_k[p] = (Xk, y)
+                sweep = MultiModelGradPlan(msgs, parts_k, prec, loss, K, d)
+                Gk = sweep.run(beta, sweep.out_buffer()[0]).reshape(len(msgs), K, ld)
+                torch.cuda.synchronize()
+                assert torch.equal(G.reshape(len(msgs), K, ld)[:, k], Gk[:, k]), f"fold model {k}"
 
 
 # ---- 2. bitwise the sweep kernel on the data with the fold's rows zeroed: the same wave layout, row and FMA order

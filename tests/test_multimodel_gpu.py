@@ -21,6 +21,7 @@ from erasurehead_amd.ops import get_precision
 from erasurehead_amd.ops.multimodel import MultiModelGradPlan
 from erasurehead_amd.ops.update import combine_update, combine_update_blocks
 from erasurehead_amd.parallel.dist import DistEnv
+import block_edge_cases as bc
 from numerics import LOSS_IDS, LOSSES, check_columns, hostile_beta, hostile_partition, oracle_message
 from test_multimodel_cpu import ALPHAS, CASES, LRS, TOL, arrival_sets, check_against_replay, make
 
@@ -87,6 +88,39 @@ def test_kernel_within_the_column_bounds(d, loss, prec_name, M, native):
         torch.cuda.synchronize()
         check(G, msgs, host, bhs, loss, prec, d, f"{'naive' if msgs is NAIVE else 'coded'} M={M}")
         assert torch.equal(G, G2)  # two launches: bitwise identical
+
+
+# ---- 1b. stage edges: ragged stages of every row count, ring reuse, tasks that start at odd rows
+STAGE_GRID = bc.scalar_grid(LOSSES)
+_edge_parts = {}
+
+
+@pytest.mark.parametrize("M", bc.SCALAR_BLOCKS)
+@pytest.mark.parametrize("d,loss,prec_name", STAGE_GRID, ids=[f"d{d}-{LOSS_IDS[l]}-{p}" for d, l, p in STAGE_GRID])
+def test_stage_edges_within_the_column_bounds(d, loss, prec_name, M, native, monkeypatch):
+    """Partitions of tests/block_edge_cases.py partition_sizes (every ragged stage around a row per wave and the full
+    stage, S + 1, 2S, 2S + 1, 3S + 2, empty), once as whole tasks of three and four stages and once cut into tasks of
+    37 rows, naive and coded messages; the same oracle, bound and checks as above."""
+    prec = get_precision(prec_name)
+    sizes, cpu_parts, host, betas = bc.scalar_inputs(d, prec_name, M)
+    if (d, prec_name, M) not in _edge_parts:
+        _edge_parts[(d, prec_name, M)] = bc.to_device(cpu_parts, DEV)
+    parts = _edge_parts[(d, prec_name, M)]
+    beta, bhs = model(betas, M)
+    for rows in bc.TASK_ROWS:
+        bc.forced_task_rows(monkeypatch, rows)
+        for kind in ("naive", "coded"):
+            msgs = bc.MESSAGES[kind](len(sizes))
+            plan = MultiModelGradPlan(msgs, parts, prec, loss, M, d)
+            assert plan.identity == (kind == "naive")
+            bc.assert_tasks_reach_the_edges(plan, sizes, bc.geometry(prec, d, M)[0], rows)
+            G = plan.out_buffer()[0].fill_(float("nan"))
+            plan.run(beta, G)
+            G2 = plan.out_buffer()[0].fill_(float("nan"))
+            plan.native_launcher().launch(beta, G2)
+            torch.cuda.synchronize()
+            check(G, msgs, host, bhs, loss, prec, d, f"{kind} M={M} tasks of {rows}")
+            assert torch.equal(G, G2)  # two launches: bitwise identical
 
 
 def test_models_do_not_leak_into_each_other(native):

@@ -23,6 +23,7 @@ from erasurehead_amd.ops import get_precision
 from erasurehead_amd.ops.multimodel import MultiModelGradPlan
 from erasurehead_amd.ops.ovr import OvrGradPlan
 from erasurehead_amd.parallel.dist import DistEnv
+import block_edge_cases as bc
 from numerics import LOSS_IDS, check_columns, hostile_beta, hostile_partition, oracle_message
 from test_multimodel_cpu import TOL
 from test_ovr_cpu import CASES, check_against_replay, make
@@ -106,6 +107,56 @@ def test_kernel_within_the_column_bounds(d, loss, prec_name, C, native):
         torch.cuda.synchronize()
         check(G, msgs, host, bhs, loss, prec, d, f"{'naive' if msgs is NAIVE else 'coded'} C={C}")
         assert torch.equal(G, G2)  # two launches: bitwise identical
+
+
+# ---- 1b. stage edges: ragged stages of every row count, ring reuse, tasks that start at odd rows
+STAGE_GRID = bc.scalar_grid(OVR_LOSSES)
+_edge_inputs = {}
+
+
+def edge_inputs(d, prec_name, C):
+    """The rows and betas of block_edge_cases.scalar_inputs with class-index labels (drawn once, never changed); the
+    partition of exactly one full stage has no row of class C - 1."""
+    key = (d, prec_name, C)
+    if key not in _edge_inputs:
+        prec = get_precision(prec_name)
+        sizes, cpu_parts, host, betas = bc.scalar_inputs(d, prec_name, C)
+        rng = np.random.RandomState(7000 + 10 * d + C)
+        lacks = bc.lacking_partition(sizes, bc.geometry(prec, d, C)[0])
+        parts, hostc = {}, {}
+        for p, n in enumerate(sizes):
+            y = rng.randint(0, C, n).astype(np.float64)
+            if p == lacks:
+                y[y == C - 1] = 0.0
+            parts[p] = (cpu_parts[p][0].to(DEV).contiguous(), torch.from_numpy(y).to(prec.acc).to(DEV).contiguous())
+            hostc[p] = (host[p][0], y)
+        _edge_inputs[key] = (sizes, parts, hostc, betas)
+    return _edge_inputs[key]
+
+
+@pytest.mark.parametrize("C", bc.SCALAR_BLOCKS)
+@pytest.mark.parametrize("d,loss,prec_name", STAGE_GRID, ids=[f"d{d}-{LOSS_IDS[l]}-{p}" for d, l, p in STAGE_GRID])
+def test_stage_edges_within_the_column_bounds(d, loss, prec_name, C, native, monkeypatch):
+    """Partitions of tests/block_edge_cases.py partition_sizes (every ragged stage around a row per wave and the full
+    stage, S + 1, 2S, 2S + 1, 3S + 2, empty), once as whole tasks of three and four stages and once cut into tasks of
+    37 rows, naive and coded messages; the same oracle, bound and checks as above."""
+    prec = get_precision(prec_name)
+    sizes, parts, host, betas = edge_inputs(d, prec_name, C)
+    beta, bhs = model(betas, C)
+    for rows in bc.TASK_ROWS:
+        bc.forced_task_rows(monkeypatch, rows)
+        for kind in ("naive", "coded"):
+            msgs = bc.MESSAGES[kind](len(sizes))
+            plan = OvrGradPlan(msgs, parts, prec, loss, C, d)
+            assert plan.identity == (kind == "naive")
+            bc.assert_tasks_reach_the_edges(plan, sizes, bc.geometry(prec, d, C)[0], rows)
+            G = plan.out_buffer()[0].fill_(float("nan"))
+            plan.run(beta, G)
+            G2 = plan.out_buffer()[0].fill_(float("nan"))
+            plan.native_launcher().launch(beta, G2)
+            torch.cuda.synchronize()
+            check(G, msgs, host, bhs, loss, prec, d, f"{kind} C={C} tasks of {rows}")
+            assert torch.equal(G, G2)  # two launches: bitwise identical
 
 
 # ---- 2. bitwise the sweep kernel on the relabelled data: the same task table, wave layout and FMA order
