@@ -106,7 +106,8 @@ class LoopbackComm : public eh::P2PComm {
  public:
   // channels: (peer, "out" | "in", staging ring device address (this process's mapping), slot bytes,
   // depth, ready flag device address, consumed flag device address, ready host address, consumed
-  // host address).  The flags are 64-bit counters in host-registered shared memory.
+  // host address).  The flags are 64-bit counters in pinned host memory of the rank that waits on them
+  // (the receiver's ready, the sender's consumed): that host address is required, the other may be 0.
   LoopbackComm(int device,
                const std::vector<std::tuple<int, std::string, uintptr_t, int64_t, int, uintptr_t, uintptr_t, uintptr_t,
                                             uintptr_t>>& chans)
@@ -116,7 +117,8 @@ class LoopbackComm : public eh::P2PComm {
     int k = 0;
     for (const auto& [peer, dir, ring, cap, depth, rdy_d, con_d, rdy_h, con_h] : chans) {
       need(dir == "out" || dir == "in", "LoopbackComm: direction is out or in");
-      need(ring && rdy_d && con_d && rdy_h && con_h && cap > 0 && cap % 16 == 0 && depth >= 1, "LoopbackComm: bad channel");
+      need(ring && rdy_d && con_d && (dir == "out" ? con_h : rdy_h) && cap > 0 && cap % 16 == 0 && depth >= 1,
+           "LoopbackComm: bad channel");
       int can = 0;
       hcheck(hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, device), "hipDeviceGetAttribute");
       need(can != 0, "LoopbackComm needs hipStreamWaitValue64");
@@ -144,8 +146,8 @@ class LoopbackComm : public eh::P2PComm {
     const uint64_t top = uint64_t{1} << 62;
     for (auto* m : {&out_, &in_})
       for (auto& [p, c] : *m) {
-        __atomic_store_n(c.ready_h, top, __ATOMIC_RELEASE);
-        __atomic_store_n(c.consumed_h, top, __ATOMIC_RELEASE);
+        if (c.ready_h) __atomic_store_n(c.ready_h, top, __ATOMIC_RELEASE);
+        if (c.consumed_h) __atomic_store_n(c.consumed_h, top, __ATOMIC_RELEASE);
       }
   }
   std::string kind() const override { return "loopback"; }

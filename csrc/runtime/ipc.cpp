@@ -7,9 +7,11 @@
 //                 handle covers exactly this buffer) that other processes open with
 //                 hipIpcOpenMemHandle (same GPU or a peer MI355X over xGMI) and view as
 //                 torch tensors;
-//  * ShmFlags   — an array of 64-bit flags in POSIX shared memory, registered with
-//                 hipHostRegister so every GPU can release-store into it while hosts
-//                 poll it with acquire loads (a flag is a monotone round counter);
+//  * ShmFlags   — an array of 64-bit flags every GPU can release-store into while the host
+//                 of the rank that owns a flag polls it with acquire loads (a flag is a
+//                 monotone round counter): each rank's flags are pinned host memory
+//                 (hipHostMalloc) the other ranks map through an IPC handle, and a small
+//                 POSIX shared-memory object carries the handles;
 //  * put_signal — one launch that copies up to 16 (src, dst) payloads and announces
 //                 each with its flag (put + signal).
 #include <c10/hip/HIPStream.h>
@@ -108,11 +110,24 @@ class IpcRegion : public std::enable_shared_from_this<IpcRegion> {
 
 class ShmFlags {
  public:
-  // register_gpu=false keeps the flags host-only (CPU tests of the polling logic).
-  ShmFlags(const std::string& name, int64_t n, bool create, bool register_gpu = true)
-      : name_(name), n_(n), owner_(create) {
+  // `owners[i]` is the rank whose host polls flag i (empty: rank 0 polls them all); `rank` is the caller's.
+  // Every rank keeps a pinned array of all n flags and flag i lives in the array of its owner, so runs
+  // of flags with one owner stay contiguous.  register_gpu=false keeps the flags in the shared-memory
+  // object itself, host-only (CPU tests of the polling logic).
+  ShmFlags(const std::string& name, int64_t n, bool create, bool register_gpu = true, int rank = 0,
+           std::vector<int> owners = {})
+      : name_(name), n_(n), owner_(create), gpu_(register_gpu), rank_(rank), owners_(std::move(owners)) {
     if (n <= 0) throw std::invalid_argument("ShmFlags: n must be > 0");
-    bytes_ = ((static_cast<size_t>(n) * 8 + 4095) / 4096) * 4096;
+    if (owners_.empty()) owners_.assign(static_cast<size_t>(n), 0);
+    if (static_cast<int64_t>(owners_.size()) != n) throw std::invalid_argument("ShmFlags: one owner per flag");
+    int world = rank + 1;
+    for (int o : owners_) {
+      if (o < 0 || o >= kMaxRanks) throw std::invalid_argument("ShmFlags: owner rank out of range");
+      world = std::max(world, o + 1);
+    }
+    if (rank < 0 || rank >= kMaxRanks) throw std::invalid_argument("ShmFlags: rank out of range");
+    flag_bytes_ = ((static_cast<size_t>(n) * 8 + 4095) / 4096) * 4096;
+    bytes_ = gpu_ ? ((sizeof(Slot) * static_cast<size_t>(world) + 4095) / 4096) * 4096 : flag_bytes_;
     fd_ = shm_open(name.c_str(), create ? (O_CREAT | O_EXCL | O_RDWR) : O_RDWR, 0600);
     if (fd_ < 0) throw std::runtime_error("shm_open(" + name + ") failed: " + std::strerror(errno));
     if (create && ftruncate(fd_, static_cast<off_t>(bytes_)) != 0) {
@@ -123,32 +138,58 @@ class ShmFlags {
     void* p = mmap(nullptr, bytes_, PROT_READ | PROT_WRITE, MAP_SHARED, fd_, 0);
     if (p == MAP_FAILED) {
       ::close(fd_);
+      if (create) shm_unlink(name.c_str());
       throw std::runtime_error("mmap failed");
     }
-    host_ = static_cast<unsigned long long*>(p);
+    map_ = p;
     if (create) std::memset(p, 0, bytes_);
-    if (register_gpu) {
-      const hipError_t e = hipHostRegister(p, bytes_, hipHostRegisterMapped | hipHostRegisterPortable);
-      if (e != hipSuccess) {
-        munmap(p, bytes_);
-        ::close(fd_);
-        if (create) shm_unlink(name.c_str());
-        host_ = nullptr;
-        hcheck(e, "hipHostRegister(flags)");
-      }
-      registered_ = true;
-      void* d = nullptr;
-      hcheck(hipHostGetDevicePointer(&d, p, 0), "hipHostGetDevicePointer(flags)");
-      dev_ = static_cast<unsigned long long*>(d);
+    if (!gpu_) {
+      host_ = static_cast<unsigned long long*>(p);
+      return;
     }
+    // this rank's flags: pinned host memory, published to the other ranks' GPUs through an IPC handle
+    void* h = nullptr;
+    void* d = nullptr;
+    hipIpcMemHandle_t handle;
+    hipError_t e = hipHostMalloc(&h, flag_bytes_, hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent);
+    const char* what = "hipHostMalloc(flags)";
+    if (e == hipSuccess) {
+      std::memset(h, 0, flag_bytes_);
+      what = "hipHostGetDevicePointer(flags)";
+      e = hipHostGetDevicePointer(&d, h, 0);
+    }
+    if (e == hipSuccess) {
+      what = "hipIpcGetMemHandle(flags)";
+      e = hipIpcGetMemHandle(&handle, h);
+    }
+    if (e != hipSuccess) {
+      if (h) hipHostFree(h);
+      munmap(p, bytes_);
+      ::close(fd_);
+      if (create) shm_unlink(name.c_str());
+      map_ = nullptr;
+      hcheck(e, what);
+    }
+    host_ = static_cast<unsigned long long*>(h);
+    dev_.assign(static_cast<size_t>(world), nullptr);
+    dev_[rank] = static_cast<unsigned long long*>(d);
+    Slot& s = static_cast<Slot*>(map_)[rank];
+    s.handle = handle;
+    __atomic_store_n(&s.ready, 1ull, __ATOMIC_RELEASE);
   }
   ~ShmFlags() { close(); }
   void close() {
-    if (!host_) return;
-    if (registered_) hipHostUnregister(host_);
-    munmap(host_, bytes_);
+    if (!map_) return;
+    if (gpu_) {
+      for (size_t r = 0; r < dev_.size(); ++r)
+        if (dev_[r] && static_cast<int>(r) != rank_) hipIpcCloseMemHandle(dev_[r]);
+      dev_.clear();
+      hipHostFree(host_);
+    }
+    munmap(map_, bytes_);
     ::close(fd_);
     unlink();
+    map_ = nullptr;
     host_ = nullptr;
   }
   // Remove the name once every process has mapped it (the mappings stay valid), so a
@@ -158,42 +199,78 @@ class ShmFlags {
     unlinked_ = true;
   }
   void check(int64_t i) const {
-    if (!host_) throw std::logic_error("ShmFlags: closed");
+    if (!map_) throw std::logic_error("ShmFlags: closed");
     if (i < 0 || i >= n_) throw std::out_of_range("ShmFlags index");
   }
-  uint64_t load(int64_t i) const {
+  bool mine(int64_t i) const { return !gpu_ || owners_[static_cast<size_t>(i)] == rank_; }
+  // Host reads and writes of another rank's flag go through the GPU (setup and reset paths only).
+  uint64_t load(int64_t i) {
     check(i);
-    return __atomic_load_n(host_ + i, __ATOMIC_ACQUIRE);
+    if (mine(i)) return __atomic_load_n(host_ + i, __ATOMIC_ACQUIRE);
+    uint64_t v = 0;
+    hcheck(hipMemcpy(&v, peer(i), sizeof(v), hipMemcpyDeviceToHost), "hipMemcpy(flag load)");
+    return v;
   }
   void store(int64_t i, uint64_t v) {
     check(i);
-    __atomic_store_n(host_ + i, v, __ATOMIC_RELEASE);
+    if (mine(i)) {
+      __atomic_store_n(host_ + i, v, __ATOMIC_RELEASE);
+      return;
+    }
+    hcheck(eh::signal_launch(peer(i), v, nullptr), "signal(flag store)");
+    hcheck(hipStreamSynchronize(nullptr), "hipStreamSynchronize(flag store)");
   }
   uintptr_t host_addr(int64_t i) const {
     check(i);
+    if (!mine(i)) throw std::logic_error("ShmFlags: flag " + std::to_string(i) + " is polled by rank " +
+                                         std::to_string(owners_[static_cast<size_t>(i)]) + ", not by this one");
     return reinterpret_cast<uintptr_t>(host_ + i);
   }
-  uintptr_t dev_addr(int64_t i) const {
+  uintptr_t dev_addr(int64_t i) {
     check(i);
-    if (!dev_) throw std::logic_error("ShmFlags: not registered with the GPU");
-    return reinterpret_cast<uintptr_t>(dev_ + i);
+    if (!gpu_) throw std::logic_error("ShmFlags: not registered with the GPU");
+    return reinterpret_cast<uintptr_t>(peer(i));
   }
   // Spin (then back off) until flag[i] >= v; false on timeout.  GIL released by the binding.
-  bool wait_ge(int64_t i, uint64_t v, double timeout) const {
+  bool wait_ge(int64_t i, uint64_t v, double timeout) {
     check(i);
-    return eh::wait_until([&] { return __atomic_load_n(host_ + i, __ATOMIC_ACQUIRE) >= v; }, timeout, 20000, 20) >= 0.0;
+    if (mine(i))
+      return eh::wait_until([&] { return __atomic_load_n(host_ + i, __ATOMIC_ACQUIRE) >= v; }, timeout, 20000, 20) >=
+             0.0;
+    return eh::wait_until([&] { return load(i) >= v; }, timeout, 0, 50) >= 0.0;
   }
   int64_t size() const { return n_; }
 
  private:
+  static constexpr int kMaxRanks = 64;
+  struct Slot {  // one per rank in the shared-memory object: where the other ranks find its flags
+    unsigned long long ready;
+    hipIpcMemHandle_t handle;
+  };
+  // Device address (in this process) of flag i in its owner's array, opening the owner's handle at first use.
+  unsigned long long* peer(int64_t i) {
+    const int o = owners_[static_cast<size_t>(i)];
+    if (!dev_[o]) {
+      Slot& s = static_cast<Slot*>(map_)[o];
+      if (!__atomic_load_n(&s.ready, __ATOMIC_ACQUIRE))
+        throw std::runtime_error("ShmFlags: rank " + std::to_string(o) + " has not opened " + name_ + " yet");
+      void* p = nullptr;
+      hcheck(hipIpcOpenMemHandle(&p, s.handle, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle(flags)");
+      dev_[o] = static_cast<unsigned long long*>(p);
+    }
+    return dev_[o] + i;
+  }
   std::string name_;
   int64_t n_;
   bool owner_;
-  size_t bytes_ = 0;
+  bool gpu_;
+  int rank_;
+  std::vector<int> owners_;
+  size_t bytes_ = 0, flag_bytes_ = 0;
   int fd_ = -1;
-  unsigned long long* host_ = nullptr;
-  unsigned long long* dev_ = nullptr;
-  bool registered_ = false;
+  void* map_ = nullptr;                   // the shared-memory object: the flags themselves, or one Slot per rank
+  unsigned long long* host_ = nullptr;    // the flags this rank's host polls
+  std::vector<unsigned long long*> dev_;  // per rank: device address of its array in this process
   bool unlinked_ = false;
 };
 
@@ -341,8 +418,9 @@ void bind_ipc(py::module& m) {
       .def_property_readonly("ptr", &IpcRegion::ptr)
       .def_property_readonly("nbytes", &IpcRegion::nbytes);
   py::class_<ShmFlags, std::shared_ptr<ShmFlags>>(m, "ShmFlags")
-      .def(py::init<const std::string&, int64_t, bool, bool>(), py::arg("name"), py::arg("n"), py::arg("create"),
-           py::arg("register_gpu") = true)
+      .def(py::init<const std::string&, int64_t, bool, bool, int, std::vector<int>>(), py::arg("name"), py::arg("n"),
+           py::arg("create"), py::arg("register_gpu") = true, py::arg("rank") = 0,
+           py::arg("owners") = std::vector<int>{})
       .def("load", &ShmFlags::load)
       .def("store", &ShmFlags::store)
       .def("host_addr", &ShmFlags::host_addr)

@@ -231,20 +231,24 @@ class CommTransport(Transport):
 
     def _loopback(self, counts):
         """Staging rings (receiver-owned IPC regions) + one shared array of 64-bit counters: per worker
-        rank r, [4r] beta ready, [4r+1] beta consumed, [4r+2] messages ready, [4r+3] messages consumed."""
+        rank r, [4r] beta ready, [4r+1] beta consumed, [4r+2] messages ready, [4r+3] messages consumed.
+        A counter lives with the rank that waits on it: the receiver's ready, the sender's consumed."""
         env, C, w = self.env, self.C, self.env.world
+        owners = [0] * (4 * w)
+        for r in range(1, w):
+            owners[4 * r] = owners[4 * r + 3] = r
         bcap = self.ld * self.es
         mcap = {r: max(16, counts.get(r, 0) * self.ld * self.es) for r in range(1, w)}
         if env.is_master:
             name = "/eh_lb_" + uuid.uuid4().hex[:16]
-            self.flags = C.ShmFlags(name, 4 * w, True)
+            self.flags = C.ShmFlags(name, 4 * w, True, True, 0, owners)
             own = {r: C.IpcRegion(self.DEPTH * mcap[r], self.dev, True) for r in range(1, w)}  # message rings
             info = (name, {r: reg.handle() for r, reg in own.items()})
         else:
             info = None
         info = env.broadcast_object(info, 0)
         if not env.is_master:
-            self.flags = C.ShmFlags(info[0], 4 * w, False)
+            self.flags = C.ShmFlags(info[0], 4 * w, False, True, env.rank, owners)
             own = {0: C.IpcRegion(self.DEPTH * bcap, self.dev, True)}  # this rank's beta ring
         self._regs += list(own.values())
         handles = env.gather_objects(None if env.is_master else own[0].handle())
@@ -252,8 +256,8 @@ class CommTransport(Transport):
         f = self.flags
 
         def ch(peer, direction, ring, cap, k):
-            return (peer, direction, ring, cap, self.DEPTH, f.dev_addr(k), f.dev_addr(k + 1), f.host_addr(k),
-                    f.host_addr(k + 1))
+            host = [f.host_addr(j) if owners[j] == env.rank else 0 for j in (k, k + 1)]
+            return (peer, direction, ring, cap, self.DEPTH, f.dev_addr(k), f.dev_addr(k + 1), host[0], host[1])
         chans = []
         if env.is_master:
             for r in range(1, w):
@@ -443,7 +447,8 @@ RcclTransport = CommTransport  # the RCCL p2p transport (kind="rccl")
 class IpcTransport(Transport):
     """HIP IPC mailboxes + put/signal kernels + shared-host round counters.
 
-    Flag layout (one ShmFlags array created by the master): index r (1..world-1) = the
+    Flag layout (one ShmFlags array created by the master; rank r's host polls its beta counter, the
+    master's host every other flag): index r (1..world-1) = the
     round counter of beta pushed to rank r (value i+1 <=> beta of round i is in the inbox),
     index world + r = the round counter of rank r's messages in the master mailbox, and from
     ``stamp_base`` on one ring of K landing stamps per rank (two words at stamp_base + 2 (r * K + i % K):
@@ -489,12 +494,13 @@ class IpcTransport(Transport):
         ibytes = self.inbox_tag_off + (self.R + 1) * TAG_BYTES
         self.stamp_base = 2 * env.world + 1
         nflags = self.stamp_base + 2 * env.world * self.K
+        owners = [r if 1 <= r < env.world else 0 for r in range(nflags)]
         if env.is_master:
             name = "/eh_" + uuid.uuid4().hex[:16]
             rbytes = self.K * max(1, self.n_rem) * (self.ld * self.es + TAG_BYTES)
 
             def _mk():
-                self.flags = C.ShmFlags(name, nflags, True)
+                self.flags = C.ShmFlags(name, nflags, True, True, 0, owners)
                 self.rreg = C.IpcRegion(rbytes, self.dev, self.FINE)
                 return (name, self.rreg.handle(), rbytes)
 
@@ -509,7 +515,7 @@ class IpcTransport(Transport):
 
             def _open():
                 name, h, rbytes = info
-                self.flags = C.ShmFlags(name, nflags, False)
+                self.flags = C.ShmFlags(name, nflags, False, True, env.rank, owners)
                 self.rremote = C.IpcRegion(h, rbytes, self.dev)
                 self._imports.append(self.rremote)
                 self.inbox_reg = C.IpcRegion(ibytes, self.dev, self.FINE)
@@ -596,7 +602,7 @@ class IpcTransport(Transport):
     def _verify(self):
         """Push a pattern both ways through the real put/signal path before training.
 
-        Catches a platform where IPC mappings or host-registered flags do not work between
+        Catches a platform where IPC mappings or the pinned host flags do not work between
         two GPUs: the engine refuses to start (or, with transport='auto', falls back to
         RCCL) instead of training on garbage.
         """
@@ -718,7 +724,7 @@ class IpcTransport(Transport):
                 us = np.sort(np.asarray(m["rtt"]))
                 out.append({"rank": r, "iters": iters, "same_gpu": p["same_gpu"],
                             "master_to_rank_peer": p["master_to_rank"], "rank_to_master_peer": p["rank_to_master"],
-                            "mailbox": "fine-grained device memory, host-registered counters" if self.FINE else "coarse",
+                            "mailbox": "fine-grained device memory, pinned host counters" if self.FINE else "coarse",
                             "rtt_clock": "device wall clock, counter store -> echo counter seen",
                             "rtt_us_p50": round(float(us[len(us) // 2]), 2),
                             "rtt_us_p99": round(float(us[min(len(us) - 1, int(0.99 * len(us)))]), 2),

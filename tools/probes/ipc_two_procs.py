@@ -17,6 +17,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from erasurehead_amd._ext import native  # noqa: E402
 
 
+OWNERS = [0, 1] + [0] * 14  # rank 1 polls its ack (flag 1); rank 0 polls the data flag and reads the time stamp
+
+
 def main():
     rank = int(os.environ["RANK"])
     world = int(os.environ["WORLD_SIZE"])
@@ -28,7 +31,7 @@ def main():
     if rank == 0:
         reg = C.IpcRegion(n * 8, dev)
         name = "/eh_probe_" + uuid.uuid4().hex[:12]
-        flags = C.ShmFlags(name, 16, True)
+        flags = C.ShmFlags(name, 16, True, True, 0, OWNERS)
         box = [(reg.handle(), name)]
     else:
         box = [None]
@@ -36,7 +39,7 @@ def main():
     if rank != 0:
         h, name = box[0]
         reg = C.IpcRegion(h, n * 8, dev)
-        flags = C.ShmFlags(name, 16, False)
+        flags = C.ShmFlags(name, 16, False, True, rank, OWNERS)
     view = reg.view("float64", [n], 0)
     counters = torch.zeros(16, dtype=torch.int32, device="cuda")
     dist.barrier()
