@@ -370,6 +370,26 @@ __device__ __forceinline__ A residual(A z, A y, A coef) {
   }
 }
 
+// residual<LOSS>(z, y, 1) and the curvature w = l''(z) of the three unweighted losses from one evaluation
+// (grad_curv.hip): logistic shares the one sigmoid, w = s (1 - s); least squares w = 2; squared hinge w = 2 where
+// y z < 1 (1 - y z > 0 holds exactly there), else 0.  r has the bits residual gives with coef = 1.
+template <int LOSS, typename A>
+__device__ __forceinline__ void residual_curvature(A z, A y, A& r, A& w) {
+  static_assert(LOSS == kLogistic || LOSS == kLeastSquares || LOSS == kSquaredHinge, "unweighted scalar losses");
+  if constexpr (LOSS == kLogistic) {
+    const A s = sigmoid_neg<A>(y * z);
+    r = -y * s;
+    w = s * (A(1) - s);
+  } else if constexpr (LOSS == kSquaredHinge) {
+    const A m = A(1) - y * z;
+    r = A(-2) * y * fmax(A(0), m);
+    w = m > A(0) ? A(2) : A(0);
+  } else {
+    r = A(-2) * (y - z);
+    w = A(2);
+  }
+}
+
 // Per-element loss of the evaluation epilogues (label y, prediction p, both widened to fp64):
 //   logistic log(1 + exp(-y p)) (stable form), least squares (y - p)^2, squared hinge max(0, 1 - y p)^2;
 //   the weighted codes w times the logistic / squared-hinge loss of (s, p), w = |y| and s the sign bit of y.

@@ -188,6 +188,12 @@ hipError_t grad_ovr_launch(int dtype, int loss, int classes, const void* segs, c
 hipError_t grad_folds_launch(int dtype, int loss, int folds, const void* segs, const void* tasks, int ntasks,
                              const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb, int d_x,
                              int ld_x, hipStream_t st, const int* gate = nullptr);
+// Gradient and Hessian diagonal of ONE scalar-loss model (grad_curv.hip; --precondition diag): beta and every Gb
+// row are [2][ld_x], Gb[p] block 0 = sum r_i x_i and block 1 = sum l''(z_i) x_i^2 over partition p at beta block 0
+// (block 1 of beta is not read).  dtype and loss as for grad_models_launch.
+hipError_t grad_curv_launch(int dtype, int loss, const void* segs, const void* tasks, int ntasks,
+                            const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb, int d_x,
+                            int ld_x, hipStream_t st, const int* gate = nullptr);
 // What grad_blocks.h answers for rows of `rowbytes` bytes and a model of `blocks` blocks: blocks_stage_rows and
 // blocks_wpg themselves (the tests hold the Python mirrors in ops/blockplan.py to them).
 void blocks_geometry(int rowbytes, int blocks, int* stage_rows, int* wpg);
@@ -285,6 +291,22 @@ static_assert(sizeof(BlockCoefs) == 16 + 3 * 8 * kMaxBlocks && sizeof(ProxCoefs)
 hipError_t combine_update_prox_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* u,
                                       double* hist, void* beta_w, double* g_out, const ProxCoefs& pc, double theta,
                                       int rule, hipStream_t st, long long* stamp = nullptr);
+// Jacobi-preconditioned (diagonal-Newton) combine + update of a [2][ld_x] model (grad_curv.hip): the messages'
+// block 0 decodes to the gradient g, block 1 to the curvature diagonal h, and per data column j
+//     P_j = gs max(h_j, 0) + l2c + damp
+//     GD:   beta'_j = beta_j - eta (gs g_j + l2c beta_j) / P_j
+//     AGD:  y = (1 - theta) beta + theta u;  beta'_j = y_j - eta (gs g_j + l2c beta_j) / P_j;  u = beta + (beta' - beta) / theta
+// with gs = gm / eta the run's gradient scale and l2c = 2 alpha.  Block 0's g is accumulated in message order with
+// combine_update's fma chain (bitwise its g_out).  Block 1 of beta_w and hist is written as exact zeros; beta and u
+// are not touched there (they start as zeros).  damp must be > 0 (and not NaN): hipErrorInvalidValue otherwise.
+struct PrecondCoefs {
+  int ld_x, d_x;
+  double eta, gs, l2c, damp, theta;
+  int rule;
+};
+hipError_t combine_update_precond_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* u,
+                                         double* hist, void* beta_w, const PrecondCoefs& pc, hipStream_t st,
+                                         long long* stamp = nullptr);
 // one device timestamp (wall_clock64, hipDeviceAttributeWallClockRate kHz) into *out
 hipError_t stamp_launch(long long* out, hipStream_t st);
 

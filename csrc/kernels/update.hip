@@ -127,6 +127,63 @@ combine_update_blocked(const CombineArgs args, const C bc, double* __restrict__ 
   if (g_out) g_out[c] = g;
 }
 
+// Jacobi-preconditioned (diagonal-Newton) combine + update of a [2][ld_x] model (launchers.h PrecondCoefs,
+// grad_curv.hip): block 0 of every message is a coded gradient, block 1 the coded curvature diagonal.  A thread per
+// element of the vector.  Column threads (c < ld_x) decode both blocks in message order -- block 0 with
+// combine_update's fma chain, so g is bitwise its g_out -- and step by
+//     P = gs max(h, 0) + l2c + damp,   step = eta (gs g + l2c beta) / P
+// (a table decode or an approximate one can leave a slightly negative h: the clamp; a NaN h stays NaN).  Block 1
+// threads keep the model's second block zero where the workers and the history read it.
+template <typename M, typename W>
+__global__ void __launch_bounds__(256)
+combine_update_precond(const CombineArgs args, const PrecondCoefs pc, double* __restrict__ beta,
+                       double* __restrict__ u, double* __restrict__ hist, W* __restrict__ beta_w,
+                       long long* __restrict__ stamp) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (stamp && c == 0) *stamp = wall_clock64();
+  if (c >= 2 * pc.ld_x) return;
+  if (c >= pc.ld_x) {  // block 1 of the model: exact zeros
+    if (beta_w) beta_w[c] = W(0);
+    if (hist) hist[c] = 0.0;
+    return;
+  }
+  if (c >= pc.d_x) {  // padded columns stay exactly zero
+    if (beta_w) beta_w[c] = W(0);
+    return;
+  }
+  double g = 0.0, h = 0.0;
+  constexpr int kBatch = 8;
+  for (int m0 = 0; m0 < args.nmsg; m0 += kBatch) {
+    double vg[kBatch], vh[kBatch];
+#pragma unroll
+    for (int k = 0; k < kBatch; ++k) {
+      const M* msg = m0 + k < args.nmsg ? static_cast<const M*>(args.msg[m0 + k]) : nullptr;
+      vg[k] = msg ? static_cast<double>(msg[c]) : 0.0;
+      vh[k] = msg ? static_cast<double>(msg[pc.ld_x + c]) : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < kBatch; ++k)
+      if (m0 + k < args.nmsg) {
+        g = fma(args.coef[m0 + k], vg[k], g);
+        h = fma(args.coef[m0 + k], vh[k], h);
+      }
+  }
+  const double b = beta[c];
+  const double P = fma(pc.gs, h < 0.0 ? 0.0 : h, pc.l2c + pc.damp);
+  const double step = pc.eta * fma(pc.gs, g, pc.l2c * b) / P;
+  double nb;
+  if (pc.rule == 0) {  // GD
+    nb = b - step;
+  } else {  // AGD (gradient and curvature evaluated at beta, as combine_update's)
+    const double yt = (1.0 - pc.theta) * b + pc.theta * u[c];
+    nb = yt - step;
+    u[c] = b + (nb - b) * (1.0 / pc.theta);
+  }
+  beta[c] = nb;
+  if (hist) hist[c] = nb;
+  if (beta_w) beta_w[c] = static_cast<W>(nb);
+}
+
 namespace {
 
 // f(M, W) for the message and worker-beta types of two dtype codes (0 fp64, 1 fp32); any other code launches nothing.
@@ -154,9 +211,23 @@ hipError_t launch_blocked(const CombineArgs& args, int msg_dtype, int w_dtype, d
 
 }  // namespace
 
-// The launchers stand in this order (prox, blocks, combine_update) because the kernels are emitted in the order of
+// The launchers stand in this order (precond, prox, blocks, combine_update) because the kernels are emitted in the order of
 // their first use: combine_update's instantiations then close the object's text as they always did (placed
 // elsewhere, the last of them gains a line of zero fill behind its s_endpgm, which tools/isa_diff.py counts).
+hipError_t combine_update_precond_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* u,
+                                         double* hist, void* beta_w, const PrecondCoefs& pc, hipStream_t st,
+                                         long long* stamp) {
+  if (pc.ld_x < 1 || pc.d_x < 1 || pc.d_x > pc.ld_x || !(pc.damp > 0.0) || (pc.rule != 0 && pc.rule != 1))
+    return hipErrorInvalidValue;  // (a NaN damping fails the comparison)
+  return dispatch_msg_w(msg_dtype, w_dtype, [&](auto m, auto w) {
+    using M = decltype(m);
+    using W = decltype(w);
+    hipLaunchKernelGGL((combine_update_precond<M, W>), dim3(ceil_div(2 * pc.ld_x, 256)), dim3(256), 0, st, args, pc,
+                       beta, u, hist, static_cast<W*>(beta_w), stamp);
+    return hipGetLastError();
+  });
+}
+
 hipError_t combine_update_prox_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* u,
                                       double* hist, void* beta_w, double* g_out, const ProxCoefs& pc, double theta,
                                       int rule, hipStream_t st, long long* stamp) {

@@ -16,7 +16,7 @@ namespace eh {
 
 struct GradLauncher {
   // 0 dense fused, 1 dense two-pass, 2 sparse, 3 multi-class softmax, 4 several scalar-loss models, 5 one-vs-rest,
-  // 6 K-fold cross-validation
+  // 6 K-fold cross-validation, 7 gradient + Hessian diagonal of one model (--precondition diag)
   int kind = 0;
   int dtype = 0, loss = 0, cpl = 0, ntasks = 0, nslots = 0, ld = 0;
   KernelChoice choice{};
@@ -30,6 +30,7 @@ struct GradLauncher {
   int acc = 0;
   int rows = 0;   // rows of G a launch writes: nslots, enc_slots after set_encode, the shared message rows (sparse dst)
   SparseArgs sa{};  // kind 2 (grad_sparse.hip); Gb is the launch's output
+  // kind 7 (grad_curv.hip): blocks = 2, block 0 the gradient and block 1 the curvature diagonal of ONE model.
   // kind 3 / 4 / 5 / 6 (grad_softmax.hip: blocks are classes; grad_multimodel.hip: models of the scalar loss `loss`;
   // grad_ovr.hip: one-vs-rest classes of the scalar loss `loss`; grad_folds.hip: fold models of the scalar loss `loss`):
   // blocks, data columns / row stride of a block (ld is the flattened blocks * ld_x), distinct partitions (the
@@ -115,6 +116,8 @@ struct GradLauncher {
       case 6:
         return grad_folds_launch(dtype, loss, blocks, segs, tasks, ntasks, stb, nparts, beta, slab, G, d_x, ld_x, st,
                                  gate);
+      case 7:
+        return grad_curv_launch(dtype, loss, segs, tasks, ntasks, stb, nparts, beta, slab, G, d_x, ld_x, st, gate);
       default:
         return hipErrorInvalidValue;
     }

@@ -283,6 +283,28 @@ class MasterPump {
     prox_ = thr;
   }
 
+  // Jacobi-preconditioned run (kernels/grad_curv.hip): the model is [2][ld_x] (d_x data columns), block 0 beta and
+  // block 1 the curvature diagonal's place, and round i divides its step by the decoded diagonal with
+  // (eta, gs, l2c, damp)[i] (launchers.h PrecondCoefs); theta and the rule stay set_schedule's.  From then on
+  // combine() launches combine_update_precond, and the rounds take neither fused update path, like a proximal run.
+  void set_precond_schedule(int ld_x, int d_x, const std::vector<double>& eta, const std::vector<double>& gs,
+                            const std::vector<double>& l2c, const std::vector<double>& damp) {
+    arb_ready_ = false;
+    need(ld_x >= 1 && d_x >= 1 && d_x <= ld_x && 2 * static_cast<int64_t>(ld_x) == ld_ && d_ == ld_,
+         "precond schedule: 2 * ld_x must be the model length");
+    need(!blocks_ && prox_.empty(), "precond schedule: not with a block or a prox schedule");
+    const size_t n = static_cast<size_t>(R_);
+    need(n > 0 && eta.size() >= n && gs.size() >= n && l2c.size() >= n && damp.size() >= n,
+         "precond schedule arrays must cover R rounds");
+    for (size_t i = 0; i < n; ++i) need(damp[i] > 0.0, "precond schedule: damping must be > 0 (and not NaN)");
+    pc_ldx_ = ld_x;
+    pc_dx_ = d_x;
+    pc_eta_ = eta;
+    pc_gs_ = gs;
+    pc_l2c_ = l2c;
+    pc_damp_ = damp;
+  }
+
   // --delay-on worker: virtual delays the collector applies to REMOTE messages (the worker ranks
   // are physically late themselves); default: the same table as the local messages.
   void set_remote_delays(const std::vector<double>& delays) {
@@ -555,7 +577,7 @@ class MasterPump {
         if (!graph) decode_round(i);
         char* g = ring_slot(G_, g_rows_, i);
         eh::LocalUpdate up;
-        if (fused_update_ && prox_.empty() && launcher_->can_fuse_update() &&
+        if (fused_update_ && prox_.empty() && pc_damp_.empty() && launcher_->can_fuse_update() &&
             local_update(i, useds[i - a], g, st + i + 1, &up)) {
           hcheck(launcher_->launch_update(beta_row(i), g, up, stream_), "local gradient + update");
           continue;
@@ -612,6 +634,7 @@ class MasterPump {
   // Why rounds [a, b) cannot run on the device arbiter ("" = they can).
   std::string device_blocker(int a, int b) const {
     if (!prox_.empty()) return "proximal step after the update (L1 penalty)";
+    if (!pc_damp_.empty()) return "preconditioned step (the update divides by the decoded curvature diagonal)";
     if (blocks_) return "per-model update coefficients (multi-model run)";
     if (comm_) return "messages travel over " + comm_->kind() + " (the arbiter polls IPC counters)";
     if (remote_.empty() || arb_src_.empty()) return "no remote workers";
@@ -854,7 +877,13 @@ class MasterPump {
       else
         eh::set_block_coefs(bc, 1, ld_, d_, &decay_[i], &gm_[i], &l2_[i]);
     };
-    if (!prox_.empty()) {  // then the soft threshold
+    if (!pc_damp_.empty()) {  // the diagonal-Newton step
+      const eh::PrecondCoefs pc{pc_ldx_, pc_dx_, pc_eta_[i], pc_gs_[i], pc_l2c_[i], pc_damp_[i], theta_[i], update_rule_};
+      hcheck(eh::combine_update_precond_launch(a, acc_, acc_, beta_.data_ptr<double>(), u_.data_ptr<double>(),
+                                               hist_.data_ptr<double>() + static_cast<int64_t>(i) * ld_,
+                                               beta_row(i + 1), pc, stream_, stamp),
+             "combine_update_precond");
+    } else if (!prox_.empty()) {  // then the soft threshold
       eh::ProxCoefs pc{};
       fill(pc);
       std::copy_n(&prox_[j], nb, pc.thr);
@@ -1156,6 +1185,9 @@ class MasterPump {
   std::vector<double> decay_, gm_, l2_, theta_, delays_, remote_delays_;
   int blocks_ = 0, block_ld_ = 0, block_dx_ = 0;  // set_block_schedule: per-model coefficients [R * blocks_]
   std::vector<double> bdecay_, bgm_, bl2_;
+  // set_precond_schedule: [R] each; pc_damp_ empty = no preconditioner
+  int pc_ldx_ = 0, pc_dx_ = 0;
+  std::vector<double> pc_eta_, pc_gs_, pc_l2c_, pc_damp_;
   std::vector<double> prox_;  // set_prox_schedule: soft thresholds [R * max(1, blocks_)]; empty = no proximal step
   int repeat_ = 1;
   int update_rule_ = 0, stop_rule_ = 0, k_ = 0;
@@ -1214,6 +1246,7 @@ void bind_master_pump(py::module& m) {
       .def("set_schedule", &MasterPump::set_schedule)
       .def("set_block_schedule", &MasterPump::set_block_schedule)
       .def("set_prox_schedule", &MasterPump::set_prox_schedule)
+      .def("set_precond_schedule", &MasterPump::set_precond_schedule)
       .def("set_decode", &MasterPump::set_decode)
       .def("add_table", &MasterPump::add_table)
       .def("begin", &MasterPump::begin, py::call_guard<py::gil_scoped_release>())

@@ -42,6 +42,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="K-fold cross-validation, K in 2..8: K models of the run's scalar loss from one pass over X per "
                         "round, model k trained without fold k (row i of a partition belongs to fold i mod K); the "
                         "evaluation reports the mean held-out loss and its spread over the folds")
+    g.add_argument("--precondition", default="none", choices=["none", "diag"],
+                   help="diag: Jacobi-preconditioned (diagonal-Newton) GD / AGD; every message carries the diagonal of "
+                        "the loss Hessian next to the gradient (one pass over X) and the master divides each column's "
+                        "step by it; --lr then multiplies a Newton-like step, so start near 1")
+    g.add_argument("--precondition-damping", type=float, default=1e-8, metavar="DELTA",
+                   help="--precondition diag: delta > 0 added to every diagonal entry (default 1e-8)")
     g.add_argument("--num-itrs", type=int, default=100)
     g.add_argument("--lr", type=float, default=10.0)
     g.add_argument("--lr-schedule", default="const", choices=["const", "invscaling", "exponential"],
@@ -158,7 +164,8 @@ def parse(argv: List[str]):
                     integrity=not a.no_integrity, delay_on=a.delay_on, slow_ranks=parse_slow_ranks(a.slow_ranks),
                     dedicated_master=a.dedicated_master, device_records=a.device_records,
                     sweep_alpha=a.alphas, sweep_lr=a.lrs, l1=a.l1, sweep_l1=a.l1s,
-                    class_weight=a.class_weight, sample_weights=a.sample_weights, ovr=a.ovr, cv=a.cv)
+                    class_weight=a.class_weight, sample_weights=a.sample_weights, ovr=a.ovr, cv=a.cv,
+                    precondition=a.precondition, precondition_damping=a.precondition_damping)
     return cfg, a
 
 

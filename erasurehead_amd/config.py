@@ -71,6 +71,11 @@ class RunConfig:
     # K-fold cross-validation, K = 2..8, of the run's scalar loss: K models that share (alpha, lr, l1), model k trained
     # without the rows of fold k, from one pass over X per round (ops/cv.py); row i of a partition is in fold i mod K
     cv: Optional[int] = None
+    # Jacobi-preconditioned (diagonal-Newton) GD / AGD: "diag" divides every column's step by the decoded diagonal of
+    # the objective's Hessian, P_j = (1/n) max(h_j, 0) + 2 alpha + damping, formed with the gradient in one pass over
+    # X (ops/precond.py); lr then multiplies a Newton-like step (values near 1).  damping: delta > 0, finite.
+    precondition: str = "none"
+    precondition_damping: float = 1e-8
     # (alpha, lr) sweep: M = 2..8 models trained in one run from one pass over X per round (ops/multimodel.py).
     # The lists are zipped; an absent list or one of length 1 is broadcast (absent: the run's alpha / lr).
     sweep_alpha: Optional[List[float]] = None
@@ -161,6 +166,7 @@ class RunConfig:
             self._check_ovr()
         if self.cv is not None:
             self._check_cv()
+        self._check_precondition()
         if self.loss == "softmax":
             self.classes = 2 if self.classes is None else int(self.classes)
             if not 2 <= self.classes <= 8:
@@ -218,6 +224,35 @@ class RunConfig:
             raise ValueError("--cv: bf16 storage is not supported (--precision fp64, fp32 or fp32x64)")
         if self.is_real and self.data != "synthetic":
             raise ValueError("--cv: sparse data sources are not supported (dense partitions only)")
+
+    def _check_precondition(self) -> None:
+        """The limits of a preconditioned run that the configuration alone decides, each a ValueError naming the flag."""
+        self.precondition = str(self.precondition)
+        if self.precondition not in ("none", "diag"):
+            raise ValueError(f"--precondition: none or diag, got {self.precondition!r}")
+        self.precondition_damping = float(self.precondition_damping)
+        if not (np.isfinite(self.precondition_damping) and self.precondition_damping > 0):
+            raise ValueError(f"--precondition-damping: must be finite and > 0, got {self.precondition_damping}")
+        if self.precondition == "none":
+            return
+        if self.loss == "softmax":
+            raise ValueError("--precondition: not supported with --loss softmax (one model of a scalar loss: "
+                             "logistic, least_squares or squared_hinge)")
+        if self.ovr is not None:
+            raise ValueError("--precondition: cannot be combined with --ovr")
+        if self.cv is not None:
+            raise ValueError("--precondition: cannot be combined with --cv")
+        if self.sweep_alpha is not None or self.sweep_lr is not None or self.sweep_l1 is not None:
+            raise ValueError("--precondition: cannot be combined with a sweep (--alphas / --lrs / --l1s)")
+        if float(self.l1) != 0:
+            raise ValueError("--precondition: cannot be combined with --l1 (a proximal step in the preconditioner's "
+                             "metric is not implemented)")
+        if self.class_weight is not None or self.sample_weights is not None:
+            raise ValueError("--precondition: --class-weight / --sample-weights are not supported")
+        if self.precision == "bf16":
+            raise ValueError("--precondition: bf16 storage is not supported (--precision fp64, fp32 or fp32x64)")
+        if self.is_real and self.data != "synthetic":
+            raise ValueError("--precondition: sparse data sources are not supported (dense partitions only)")
 
     def _sweep_lists(self) -> Optional[Tuple[List[float], List[float], List[float]]]:
         """([alpha_k], [lr_k], [l1_k]) of a sweep run, every list broadcast to the M models; None without a list."""

@@ -1,8 +1,10 @@
 """What kind of model a run trains, decided once (ModelSpec), and its update schedule (UpdateSchedule).
 
-Five kinds share the engine: a ``single`` model of a scalar loss, ``softmax`` and one-vs-rest (``ovr``) with one
-block per class, a ``sweep`` of M (alpha, lr, l1) models of one scalar loss, and the K fold models of a K-fold
-cross-validation (``cv``) of one scalar loss.  Everything the engine keeps
+Six kinds share the engine: a ``single`` model of a scalar loss, ``softmax`` and one-vs-rest (``ovr``) with one
+block per class, a ``sweep`` of M (alpha, lr, l1) models of one scalar loss, the K fold models of a K-fold
+cross-validation (``cv``) of one scalar loss, and a single model stepped by a Jacobi preconditioner (``precond``,
+--precondition diag: block 0 is the model, block 1 the place of the curvature diagonal in every message and exact
+zeros in the model).  Everything the engine keeps
 (beta, messages, history, checkpoints) is one vector of ``ld`` elements, block-major ``[blocks][ld_x]`` with
 ``ld_x = prec.ld(d_x)`` and the padding columns of every block exactly zero; ``d`` of them are stored per round.
 A single model is one block with ``d = d_x``; the other kinds have ``d = ld = blocks * ld_x``.
@@ -25,13 +27,15 @@ from ..ops.grad import DenseGradPlan, SharedGradPlan, SparseGradPlan
 from ..ops.multimodel import MultiModelGradPlan
 from ..ops.ovr import OvrGradPlan
 from ..ops.precision import Precision
+from ..ops.precond import PrecondGradPlan
 from ..ops.softmax import SoftmaxGradPlan
-from ..ops.update import combine_update, combine_update_blocks, combine_update_prox
+from ..ops.update import combine_update, combine_update_blocks, combine_update_precond, combine_update_prox
 
 SQHINGE_PREFIX = "sqhinge_"  # result files of squared-hinge runs (next to the logistic names)
 SOFTMAX_PREFIX = "softmax_"
 OVR_PREFIX = "ovr_"  # result files of one-vs-rest runs (before sqhinge_)
 WEIGHTED_PREFIX = "weighted_"  # result files of runs with class / sample weights
+PRECOND_PREFIX = "precond_"  # result files of --precondition diag runs (before sqhinge_)
 
 
 def sweep_prefix(k: int) -> str:
@@ -44,7 +48,7 @@ def cv_prefix(k: int) -> str:
 
 @dataclass(frozen=True)
 class ModelSpec:
-    kind: str  # "single" | "softmax" | "ovr" | "sweep" | "cv"
+    kind: str  # "single" | "softmax" | "ovr" | "sweep" | "cv" | "precond"
     loss: int  # models/losses.py code, the weighted code of a weighted run; one-vs-rest: the binary loss
     weighted: bool  # class / sample weights: the labels carry them (data/source.py WeightedSource)
     classes: int  # softmax, one-vs-rest: the class blocks; 1 otherwise
@@ -62,6 +66,9 @@ class ModelSpec:
     cv: int = 0
     fold_rows: Optional[Tuple[int, ...]] = None
     n_rows: int = 0
+    # --precondition diag: "diag" and the damping delta > 0 of P = gs max(h, 0) + 2 alpha + delta; "none" / 0.0 without
+    precondition: str = "none"
+    damping: float = 0.0
 
     # ---------------------------------------------------------------- resolution and rejections
     @classmethod
@@ -98,7 +105,7 @@ class ModelSpec:
         sweep = cfg.sweep()
         if sweep:
             kind = "sweep"
-        models, cv = (len(sweep) if sweep else 1), {}
+        models, extra = (len(sweep) if sweep else 1), {}  # extra: the constructor keywords of --cv / --precondition
         if cfg.cv is not None:
             kind, models = "cv", int(cfg.cv)
             # the fold counts, and with them n / (n - n_k), assume what the scheme does: equal partitions that add up
@@ -107,15 +114,22 @@ class ModelSpec:
                 raise ValueError(f"--cv: n_rows = {cfg.n_rows} is not {scheme.n_partition_files} partitions of equal "
                                  f"size; the fold counts need n_rows to be a multiple of the partition count")
             per_part = CvGradPlan.fold_rows(scheme.rows_per_partition, models)
-            cv = dict(cv=models, fold_rows=tuple(int(scheme.n_partition_files) * f for f in per_part),
-                      n_rows=int(cfg.n_rows))
-            if max(cv["fold_rows"]) >= cv["n_rows"]:
-                raise ValueError(f"--cv: a fold holds every row ({cv['fold_rows']} of {cv['n_rows']}): its model "
+            extra = dict(cv=models, fold_rows=tuple(int(scheme.n_partition_files) * f for f in per_part),
+                         n_rows=int(cfg.n_rows))
+            if max(extra["fold_rows"]) >= extra["n_rows"]:
+                raise ValueError(f"--cv: a fold holds every row ({extra['fold_rows']} of {extra['n_rows']}): its model "
                                  f"would have nothing to train on")
+        if cfg.precondition != "none":  # (the config rejected what it can see; these need the resolved run)
+            if kind != "single":
+                raise ValueError(f"--precondition: not supported with a {kind} model (one model of a scalar loss)")
+            if weighted:  # a source that brings sample weights of its own
+                raise ValueError("--precondition: class / sample weights are not supported")
+            kind = "precond"
+            extra = dict(precondition=str(cfg.precondition), damping=float(cfg.precondition_damping))
         d_x = int(cfg.n_cols)
         spec = cls(kind, loss, weighted, classes, models, d_x, prec.ld(d_x), float(cfg.l1),
                    [a for a, _ in sweep] if sweep else None, [x for _, x in sweep] if sweep else None,
-                   cfg.sweep_l1s(), prec, bool(sparse), **cv)
+                   cfg.sweep_l1s(), prec, bool(sparse), **extra)
         if kind == "softmax":
             SoftmaxGradPlan.check_supported(prec, classes, sparse)
         elif kind == "ovr":
@@ -124,6 +138,8 @@ class ModelSpec:
             MultiModelGradPlan.check_supported(prec, loss, spec.models, sparse, spec.ld_x, gpu)
         elif kind == "cv":
             CvGradPlan.check_supported(prec, loss, spec.models, sparse, spec.ld_x, gpu)
+        elif kind == "precond":
+            PrecondGradPlan.check_supported(prec, loss, sparse, spec.ld_x, gpu)
         return spec
 
     def check_partitions(self, parts, rows_per_partition: int) -> None:
@@ -138,8 +154,14 @@ class ModelSpec:
 
     # ------------------------------------------------------------------------------- the layout
     @property
-    def blocks(self) -> int:
+    def model_blocks(self) -> int:
+        """The blocks that are models: classes, a sweep's models, fold models; 1 for a single model."""
         return self.classes * self.models
+
+    @property
+    def blocks(self) -> int:
+        """The blocks of the vector: a preconditioned run's model is followed by the curvature diagonal's block."""
+        return 2 if self.kind == "precond" else self.model_blocks
 
     @property
     def ld(self) -> int:
@@ -186,26 +208,29 @@ class ModelSpec:
         return self.classes if self.blocked else None
 
     def pack(self, x) -> np.ndarray:
-        """[..., blocks, d_x] -> [..., ld]: every block in its ld_x columns, the padding columns zero."""
+        """[..., model blocks, d_x] -> [..., ld]: every block in its ld_x columns, the padding columns (and a
+        preconditioned run's second block) zero."""
         x = np.asarray(x, dtype=np.float64)
-        if x.shape[-2:] != (self.blocks, self.d_x):
-            raise ValueError(f"expected [..., {self.blocks}, {self.d_x}], got {list(x.shape)}")
-        out = np.zeros(x.shape[:-1] + (self.ld_x,))
-        out[..., : self.d_x] = x
+        if x.shape[-2:] != (self.model_blocks, self.d_x):
+            raise ValueError(f"expected [..., {self.model_blocks}, {self.d_x}], got {list(x.shape)}")
+        out = np.zeros(x.shape[:-2] + (self.blocks, self.ld_x))
+        out[..., : self.model_blocks, : self.d_x] = x
         return out.reshape(x.shape[:-2] + (self.ld,))
 
     def unpack(self, betaset) -> np.ndarray:
-        """A trajectory [R, d] (or packed [R, ld]) viewed as [R, blocks, d_x]."""
+        """A trajectory [R, d] (or packed [R, ld]) viewed as [R, model blocks, d_x]."""
         B = np.asarray(betaset)
         if B.ndim != 2 or B.shape[1] not in (self.d, self.ld):
             raise ValueError(f"expected [R, {self.d}] or [R, {self.ld}], got {list(B.shape)}")
-        return B.reshape(B.shape[0], self.blocks, -1)[:, :, : self.d_x]
+        return B.reshape(B.shape[0], self.blocks, -1)[:, : self.model_blocks, : self.d_x]
 
     def rows(self, betaset) -> np.ndarray:
-        """A trajectory [R, d] as the [R * blocks, ld_x] model matrix of the evaluation GEMMs."""
+        """A trajectory [R, d] as the [R * model blocks, ld_x] model matrix of the evaluation GEMMs."""
         B = np.asarray(betaset, dtype=np.float64)
         full = np.zeros((B.shape[0], self.ld))
         full[:, : self.d] = B
+        if self.kind == "precond":  # scored as the single model in block 0
+            return np.ascontiguousarray(full[:, : self.ld_x])
         return full.reshape(B.shape[0] * self.blocks, self.ld_x)
 
     def beta0(self, init_zero: bool, seed: Optional[int]) -> np.ndarray:
@@ -220,7 +245,7 @@ class ModelSpec:
         else:
             b0 = np.random.randn(nb)
         return self.pack(np.broadcast_to(b0.reshape(self.classes, 1, self.d_x),
-                                         (self.classes, self.models, self.d_x)).reshape(self.blocks, self.d_x))
+                                         (self.classes, self.models, self.d_x)).reshape(self.model_blocks, self.d_x))
 
     def sparsity(self, betaset) -> Tuple[np.ndarray, np.ndarray]:
         """(nnz, l1 * ||beta||_1) of every iterate over the data columns: [R], or [R, M] for a sweep (softmax and
@@ -244,6 +269,8 @@ class ModelSpec:
             return MultiModelGradPlan(messages, parts, self.prec, self.loss, self.models, self.d_x)
         if self.kind == "cv":
             return CvGradPlan(messages, parts, self.prec, self.loss, self.models, self.d_x)
+        if self.kind == "precond":
+            return PrecondGradPlan(messages, parts, self.prec, self.loss, self.d_x)
 
         def one(msgs):
             if self.sparse:
@@ -292,9 +319,10 @@ class ModelSpec:
 
     def result_names(self, names: Dict[str, str], model_prefix: str = "") -> Dict[str, str]:
         """The scheme's result names under the run's prefixes: ``sweep{k}_`` / ``cv{k}_`` first, then ``softmax_`` /
-        ``ovr_``, ``weighted_``, ``sqhinge_``."""
+        ``ovr_``, ``weighted_``, ``precond_``, ``sqhinge_``."""
         p = model_prefix + {"softmax": SOFTMAX_PREFIX, "ovr": OVR_PREFIX}.get(self.kind, "")
-        p += (WEIGHTED_PREFIX if self.weighted else "") + (SQHINGE_PREFIX if base_kind(self.loss) == SQUARED_HINGE else "")
+        p += (WEIGHTED_PREFIX if self.weighted else "") + (PRECOND_PREFIX if self.kind == "precond" else "")
+        p += (SQHINGE_PREFIX if base_kind(self.loss) == SQUARED_HINGE else "")
         return {k: p + v for k, v in names.items()}
 
     # ----------------------------------------------------------------------------- its identity
@@ -307,6 +335,8 @@ class ModelSpec:
             rep.update(ovr=True, classes=self.classes)
         if self.kind == "cv":
             rep.update(cv=self.cv, fold_rows=list(self.fold_rows))
+        if self.kind == "precond":
+            rep.update(precondition=self.precondition, damping=self.damping)
         rep.update(l1=list(self.sweep_l1) if self.kind == "sweep" else self.l1, prox=bool(self.prox),
                    weighted=bool(self.weighted))
         return rep
@@ -325,6 +355,9 @@ class ModelSpec:
             state["ovr"] = int(self.classes)
         if self.kind == "cv":
             state["cv"] = int(self.cv)
+        if self.kind == "precond":
+            state["precondition"] = self.precondition
+            state["precondition_damping"] = float(self.damping)
         return state
 
     def check_checkpoint(self, st, path: str, weight_spec) -> None:
@@ -353,6 +386,11 @@ class ModelSpec:
         if have_cv != want_cv:
             raise ValueError(f"checkpoint {path} was written by a run with cv = {have_cv}; this run has "
                              f"cv = {want_cv} (--cv)")
+        have_pc = (st.get("precondition", "none"), float(st.get("precondition_damping", 0.0)))
+        if have_pc != (self.precondition, float(self.damping)):
+            raise ValueError(f"checkpoint {path} was written by a run with precondition = {have_pc[0]}, damping = "
+                             f"{have_pc[1]:g}; this run has precondition = {self.precondition}, damping = "
+                             f"{self.damping:g} (--precondition / --precondition-damping)")
         have_w = st.get("weights")
         if have_w != weight_spec:
             raise ValueError(f"checkpoint {path} was written by a run with weights = {have_w}; this run has "
@@ -376,6 +414,10 @@ class UpdateSchedule:
     block_d: int
     # a sweep's pump is also given the single-model rows of the run's own (alpha, lr), [3, R]: decay, gm, l2
     single: np.ndarray
+    # --precondition diag: [4, R] eta, gs, l2c, damping of the diagonal-Newton step (UpdateRule.precond_coeffs) and one
+    # block of the [2][ld_x] vector; None without
+    precond: Optional[np.ndarray] = None
+    precond_block: Tuple[int, int] = (0, 0)
 
     @classmethod
     def build(cls, rule: UpdateRule, rounds: int, eta, sweep_etas, spec: ModelSpec) -> "UpdateSchedule":
@@ -402,13 +444,22 @@ class UpdateSchedule:
                    else [rule.threshold(i, float(eta[i]))] for i in range(R)]
             thr = np.array(thr, dtype=np.float64).reshape(R, -1)
             thr = np.repeat(thr, B, axis=1) if spec.kind == "cv" else thr.reshape(R, B)
-        return cls(decay, gm, l2, thr, theta, code, *block, single)
+        precond, pblock = None, (0, 0)
+        if spec.kind == "precond":
+            pco = [rule.precond_coeffs(i, float(eta[i])) for i in range(R)]
+            precond = np.array([[c[k] for c in pco] for k in range(3)] + [[spec.damping] * R],
+                               dtype=np.float64).reshape(4, R)
+            pblock = (spec.ld_x, spec.d_x)
+        return cls(decay, gm, l2, thr, theta, code, *block, single, precond, pblock)
 
     def apply(self, i: int, msgs, coefs, beta, u, hist, beta_w) -> None:
         """Round i's combine + update (ops/update.py): with a threshold the proximal form (a single model as one
         block), a sweep without one the blocked form, anything else the plain one."""
         theta = float(self.theta[i])
-        if self.thr is not None:
+        if self.precond is not None:
+            combine_update_precond(msgs, coefs, beta, u, *self.precond_block, *(float(x) for x in self.precond[:, i]),
+                                   theta, self.code, hist=hist, beta_w=beta_w)
+        elif self.thr is not None:
             combine_update_prox(msgs, coefs, beta, u, self.block_ld, self.block_d, self.decay[i].tolist(),
                                 self.gm[i].tolist(), self.l2[i].tolist(), self.thr[i].tolist(), theta, self.code,
                                 hist=hist, beta_w=beta_w)
@@ -429,3 +480,5 @@ class UpdateSchedule:
                                     self.gm.ravel().tolist(), self.l2.ravel().tolist())
         if self.thr is not None:  # soft thresholds [R] or [R * M]; the rounds then stay off both fused update paths
             pump.set_prox_schedule(self.thr.ravel().tolist())
+        if self.precond is not None:  # the rounds then stay off both fused update paths, like a proximal run's
+            pump.set_precond_schedule(*self.precond_block, *(x.tolist() for x in self.precond))

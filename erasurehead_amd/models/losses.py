@@ -265,6 +265,39 @@ def cv_grad(kind: int, X, y: np.ndarray, B: np.ndarray, coef=None) -> np.ndarray
     return np.stack([_GRADS[kind](X[keep[:, k]], y[keep[:, k]], B[k], coef) for k in range(B.shape[0])])
 
 
+def curvature(kind: int, z, y) -> np.ndarray:
+    """The second derivative l''(z) of the per-row loss whose first derivative is the worker gradient's residual:
+    logistic s (1 - s) with s = sigmoid(-y z), least squares 2, squared hinge 2 where y z < 1 and 0 elsewhere."""
+    z, y = np.asarray(z, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if kind == LOGISTIC:
+        s = _sigmoid_neg(y * z)
+        return s * (1.0 - s)
+    if kind == LEAST_SQUARES:
+        return np.full_like(z, 2.0)
+    if kind == SQUARED_HINGE:
+        return np.where(1.0 - y * z > 0.0, 2.0, 0.0)
+    raise ValueError(f"preconditioned: loss kind {kind} is not logistic, least squares or squared hinge")
+
+
+def precond_grad(kind: int, X, y: np.ndarray, beta: np.ndarray, coef=None) -> np.ndarray:
+    """[2, d]: row 0 the scalar-loss gradient sum r_i x_i at beta, row 1 the diagonal of its Hessian
+    sum l''(z_i) x_i^2 (what one partition contributes to a --precondition diag message, times coef)."""
+    X = np.asarray(X, dtype=np.float64)
+    w = curvature(kind, X.dot(beta), y)
+    h = (X * X).T.dot(w)
+    return np.stack([_GRADS[kind](X, y, beta, coef), h if coef is None else coef * h])
+
+
+def precond_unpack(betaset: np.ndarray, d_x: Optional[int] = None) -> np.ndarray:
+    """[R, 2 * ld_x] trajectory of a --precondition diag run (as the engine stores it) -> block 0 [R, d_x], the
+    model (d_x absent: all ld_x columns); block 1 is the curvature diagonal's place on the wire and stays zero."""
+    b = np.asarray(betaset)
+    b = b.reshape(1, -1) if b.ndim == 1 else b
+    if b.shape[1] % 2 or (d_x is not None and b.shape[1] // 2 < d_x):
+        raise ValueError(f"model length {b.shape[1]} is not two blocks of >= {d_x or 1} columns")
+    return b[:, : (b.shape[1] // 2 if d_x is None else int(d_x))]
+
+
 def worker_grad(kind: int, X, y, beta, coef=None) -> np.ndarray:
     if kind == SOFTMAX:  # beta: the flattened [C, X.shape[1]] model; returns the gradient flattened alike
         d = X.shape[1]
@@ -377,6 +410,29 @@ class UpdateRule:
     def block_thresholds(self, i: int, etas, l1s):
         """Round i of a sweep run: [t_k] with model k's step etas[k] and L1 strength l1s[k]."""
         return [dataclasses.replace(self, l1=float(l)).threshold(i, float(e)) for e, l in zip(etas, l1s)]
+
+    def precond_coeffs(self, i: int, eta: float) -> Tuple[float, float, float, float, int]:
+        """(eta, gs, l2c, theta, rule_code) of round i's preconditioned step: gs = gm / eta is the scale coeffs()
+        gives the gradient (1 / n, avoidstragg's rescale included) and l2c = 2 alpha the L2 term's curvature."""
+        _, _, _, theta, code = self.coeffs(i, eta)
+        return float(eta), self.grad_scale / self.n_samples, 2.0 * self.alpha, theta, code
+
+    def step_precond(self, i: int, eta: float, beta: np.ndarray, u: np.ndarray, g: np.ndarray, h: np.ndarray,
+                     damping: float) -> None:
+        """In-place Jacobi-preconditioned (diagonal-Newton) update from the decoded gradient g and curvature diagonal
+        h (oracle of combine_update_precond): P = gs max(h, 0) + 2 alpha + damping, step = eta (gs g + 2 alpha beta) / P,
+        GD beta -= step, AGD as apply() with the step in place of gm g + l2 beta."""
+        if not (np.isfinite(damping) and damping > 0):
+            raise ValueError(f"--precondition-damping must be finite and > 0, got {damping}")
+        eta, gs, l2c, theta, code = self.precond_coeffs(i, eta)
+        P = gs * np.where(h < 0, 0.0, h) + l2c + damping
+        step = eta * (gs * g + l2c * beta) / P
+        if code == 0:
+            beta -= step
+        else:
+            betatemp = (1 - theta) * beta + theta * u - step
+            u[:] = beta + (betatemp - beta) * (1 / theta)
+            beta[:] = betatemp
 
     def apply(self, i: int, eta: float, beta: np.ndarray, u: np.ndarray, g: np.ndarray) -> None:
         """In-place host update (oracle of the combine_update kernel; with l1 > 0 of combine_update_prox: the new

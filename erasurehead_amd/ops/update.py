@@ -49,6 +49,49 @@ def combine_update_prox(msgs: Sequence[torch.Tensor], coefs: Sequence[float], be
                     hist, beta_w, g_out)
 
 
+def combine_update_precond(msgs: Sequence[torch.Tensor], coefs: Sequence[float], beta: torch.Tensor, u: torch.Tensor,
+                           ld_x: int, d_x: int, eta: float, gs: float, l2c: float, damp: float, theta: float,
+                           rule: int, hist: Optional[torch.Tensor] = None,
+                           beta_w: Optional[torch.Tensor] = None) -> None:
+    """The Jacobi-preconditioned (diagonal-Newton) combine + update of a ``[2][ld_x]`` model (ops/precond.py): block 0
+    of the messages decodes to the gradient g, block 1 to the curvature diagonal h, and per data column
+    ``P = gs * max(h, 0) + l2c + damp``, ``step = eta * (gs * g + l2c * beta) / P``; GD ``beta -= step``, AGD
+    ``beta' = (1 - theta) beta + theta u - step`` with the usual momentum.  Block 1 of beta_w and hist is written as
+    zeros.  Native on GPU tensors, torch on CPU tensors."""
+    ld_x, d_x, damp = int(ld_x), int(d_x), float(damp)
+    if not (1 <= d_x <= ld_x and beta.numel() == 2 * ld_x and u.numel() == 2 * ld_x):
+        raise ValueError(f"combine_update_precond: two blocks of {ld_x} columns do not describe this model")
+    if not (damp > 0.0 and damp != float("inf")):
+        raise ValueError(f"combine_update_precond: the damping must be finite and > 0, got {damp}")
+    if beta.is_cuda:
+        C = native()
+        if len(msgs) > C.MAX_MSGS:
+            raise ValueError(f"at most {C.MAX_MSGS} messages per combine")
+        C.combine_update_precond(list(msgs), [float(c) for c in coefs], beta, u, hist, beta_w, ld_x, d_x, float(eta),
+                                 float(gs), float(l2c), damp, float(theta), int(rule))
+        return
+    g = torch.zeros(d_x, dtype=torch.float64)
+    h = torch.zeros(d_x, dtype=torch.float64)
+    for m, c in zip(msgs, coefs):
+        g += float(c) * m[:d_x].double()
+        h += float(c) * m[ld_x: ld_x + d_x].double()
+    b = beta[:d_x]
+    P = gs * torch.where(h < 0, torch.zeros_like(h), h) + (l2c + damp)
+    step = eta * (gs * g + l2c * b) / P
+    if rule == 0:
+        nb = b - step
+    else:
+        nb = (1.0 - theta) * b + theta * u[:d_x] - step
+        u[:d_x] = b + (nb - b) * (1.0 / theta)
+    beta[:d_x] = nb
+    if hist is not None:
+        hist[:d_x] = nb
+        hist[ld_x:] = 0.0
+    if beta_w is not None:
+        beta_w.zero_()
+        beta_w[:d_x] = nb.to(beta_w.dtype)
+
+
 def _update_blocked(name, msgs, coefs, beta, u, block_ld, d_x, decay, gm, l2, thr, theta, rule, hist, beta_w,
                     g_out) -> None:
     """The two blocked forms: ``thr`` None is combine_update_blocks, a sequence is combine_update_prox."""

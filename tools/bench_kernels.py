@@ -164,6 +164,7 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
     from erasurehead_amd.ops.multimodel import MultiModelGradPlan
     from erasurehead_amd.ops.cv import CvGradPlan
     from erasurehead_amd.ops.ovr import OvrGradPlan
+    from erasurehead_amd.ops.precond import PrecondGradPlan
 
     layouts = {"naive": [[p] for p in range(8)], "agc": [[0, 1, 2]] * 3 + [[3, 4, 5]] * 3 + [[6, 7]] * 2}
     if layouts_only:
@@ -219,6 +220,20 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
                                 out.append(r)
                                 print(json.dumps(r), flush=True)
                                 del plan, G
+                            continue
+                        if loss == "precond":  # gradient + Hessian diagonal of one model: hold against multimodel M = 2
+                            plan = PrecondGradPlan([[(p, 1.0) for p in m] for m in msgs], parts, prec,
+                                                   LOSS_NAMES["logistic"], d)
+                            b2 = torch.randn(plan.ld, device="cuda", dtype=prec.acc) * 0.01
+                            G = plan.out_buffer()[0]
+                            ms = _time(lambda: plan.run(b2, G), reps=20)
+                            distinct = 8 * nbytes / 1e12  # TB
+                            r = {"kernel": "grad_curv_sweep", "precision": prec_name, "d": d, "n": n, "layout": lay,
+                                 "loss": "logistic", "tasks": plan.ntasks, "ms": ms, "distinct_TBps": distinct / ms * 1e3,
+                                 "copy_TBps": ceiling, "frac": distinct / ms * 1e3 / ceiling}
+                            out.append(r)
+                            print(json.dumps(r), flush=True)
+                            del plan, G
                             continue
                         if loss == "ovr":
                             for C in classes:
@@ -426,6 +441,9 @@ def main():
     ap.add_argument("--cv", default=None, metavar="K,...",
                     help="--only sweep: also run the cross-validation kernel (grad_folds) for these fold counts, e.g. "
                          "2,4,8; with --loss multimodel --models 2,4,8 the sweep kernel at M = K runs next to it")
+    ap.add_argument("--precond", action="store_true",
+                    help="--only sweep: also run the preconditioned run's kernel (grad_curv: gradient + Hessian "
+                         "diagonal of one logistic model), to hold against --loss multimodel --models 2")
     ap.add_argument("--weighted", action="store_true",
                     help="--only sweep / sparse: the weighted code of the loss on labels y * w, w = 10**U(-2, 2) (logistic, "
                          "squared_hinge; sparse: logistic) -- compare with a run without the flag")
@@ -459,9 +477,11 @@ def main():
     losses = tuple(a.loss.split(","))
     if a.cv and "cv" not in losses:  # (``cv`` may also be named in --loss, to alternate it with the other kernels)
         losses += ("cv",)
-    if any(x not in LOSS_CHOICES and x not in ("multimodel", "ovr", "cv") for x in losses):
-        ap.error(f"--loss: names from {sorted(LOSS_CHOICES) + ['multimodel', 'ovr', 'cv']}")
-    if a.weighted and any(x in ("least_squares", "softmax", "multimodel", "ovr", "cv") for x in losses):
+    if a.precond and "precond" not in losses:  # (may also be named in --loss, to alternate it with the other kernels)
+        losses += ("precond",)
+    if any(x not in LOSS_CHOICES and x not in ("multimodel", "ovr", "cv", "precond") for x in losses):
+        ap.error(f"--loss: names from {sorted(LOSS_CHOICES) + ['multimodel', 'ovr', 'cv', 'precond']}")
+    if a.weighted and any(x in ("least_squares", "softmax", "multimodel", "ovr", "cv", "precond") for x in losses):
         ap.error("--weighted: logistic or squared_hinge (no other kernel has a weighted instance)")
     out = []
     if a.only in (None, "dense"):
