@@ -6,6 +6,10 @@
 
 namespace eh {
 
+// Beside launchers.h kSlabSplits, the other two numbers that pick a reduction kernel: a put of at most kPutOneSlots
+// messages and kPutOneElems elements (nslots * ld) takes the one-block slab_reduce_final_put1 in the two-stage forms.
+constexpr int kPutOneElems = 4096, kPutOneSlots = 16;
+
 // The form set_slab_reduce_mode chose.  put (optional): the worker's message put + signal rides the final
 // reduction kernel (put_protocol.h); put->gate must be `gate`.
 hipError_t slab_reduce_launch(int dtype, const void* slab, const int* stb, void* part, void* G, int nslots, int ld,

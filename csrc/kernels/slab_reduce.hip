@@ -174,8 +174,8 @@ slab_reduce_final_put(const A* __restrict__ part, A* __restrict__ G, int ld, Put
 // ONE 1024-thread block: no cross-block counter and no second release -- the block sums its
 // elements two at a time (32 split loads in flight per thread), keeps the tag checksums in LDS
 // (integer adds, order-free), writes the tags, releases once and stores the flag.  The multi-block
-// form pays a device-scope atomic round trip and the last block's own release on top.
-constexpr int kPutOneElems = 4096, kPutOneSlots = 16;
+// form pays a device-scope atomic round trip and the last block's own release on top.  (kPutOneElems,
+// kPutOneSlots: slab_reduce.h.)
 
 template <typename A>
 __global__ void __launch_bounds__(1024)
