@@ -307,6 +307,26 @@ struct PrecondCoefs {
 hipError_t combine_update_precond_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* u,
                                          double* hist, void* beta_w, const PrecondCoefs& pc, hipStream_t st,
                                          long long* stamp = nullptr);
+// Limited-memory BFGS combine + update of ONE model of a scalar loss (lbfgs.hip; --lbfgs M): one launch of one
+// workgroup.  The messages decode to g with combine_update's fma chain, G = gs g + l2c beta, and the step is the
+// two-loop recursion over the pairs the state holds, beta' = beta - tau p, or the GD step beta' = beta - eta G while no
+// pair is held or when p is no descent direction (the ring is then emptied).  Everything the method remembers lives on
+// the device and the kernel itself advances it:
+//   state [2 memory + 3][ld] fp64: rows [0, memory) the ring's s vectors, [memory, 2 memory) its y vectors (physical
+//         slots), then beta_prev, G_prev and a scratch row that holds the last step's direction (p, or G of a GD step)
+//   ring  int32 [4]: head (physical slot of the oldest pair), count, 1 once a round has been seen, the last step's
+//         mode (0 quasi-Newton, 1 GD without a pair, 2 GD and the ring emptied)
+// A fresh run starts from zeros.  memory outside 1..kLbfgsMaxMemory, d outside 1..ld, a tau that is not finite and
+// > 0, or an unknown dtype is hipErrorInvalidValue and nothing is launched.  gate: common.h gate_closed.
+constexpr int kLbfgsMaxMemory = 7;  // 2 * 7 + 1 columns fill one 16-wide MFMA tile
+struct LbfgsCoefs {
+  int ld, d;
+  double eta, gs, l2c, tau;
+  int memory;
+};
+hipError_t lbfgs_update_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* hist,
+                               void* beta_w, double* state, int* ring, const LbfgsCoefs lc, hipStream_t st,
+                               long long* stamp = nullptr, const int* gate = nullptr);
 // one device timestamp (wall_clock64, hipDeviceAttributeWallClockRate kHz) into *out
 hipError_t stamp_launch(long long* out, hipStream_t st);
 

@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <map>
 #include <memory>
@@ -305,6 +306,35 @@ class MasterPump {
     pc_damp_ = damp;
   }
 
+  // Limited-memory BFGS run (kernels/lbfgs.hip; --lbfgs M): one model of a scalar loss, round i steps by the two-loop
+  // recursion with (eta, gs, l2c)[i] and the constant step tau (launchers.h LbfgsCoefs).  The pump owns the state the
+  // method keeps between rounds (ring, beta_prev, G_prev, head and count: lbfgs_state()), zeroed here; the kernel
+  // advances it on the device, so a captured graph of the rounds replays unchanged.  From then on combine() launches
+  // lbfgs_update, and the rounds take neither fused update path, like a preconditioned run.  Call after set_state.
+  void set_lbfgs_schedule(int memory, double tau, const std::vector<double>& eta, const std::vector<double>& gs,
+                          const std::vector<double>& l2c) {
+    arb_ready_ = false;
+    need(memory >= 1 && memory <= eh::kLbfgsMaxMemory, "lbfgs schedule: memory must be in 1..7");
+    need(tau > 0.0 && std::isfinite(tau), "lbfgs schedule: the step must be finite and > 0");
+    need(!blocks_ && prox_.empty() && pc_damp_.empty() && update_rule_ == 0,
+         "lbfgs schedule: one GD model, not with a block, prox or precond schedule");
+    need(beta_.defined(), "lbfgs schedule: set_state first");
+    const size_t n = static_cast<size_t>(R_);
+    need(n > 0 && eta.size() >= n && gs.size() >= n && l2c.size() >= n, "lbfgs schedule arrays must cover R rounds");
+    lb_memory_ = memory;
+    lb_tau_ = tau;
+    lb_eta_ = eta;
+    lb_gs_ = gs;
+    lb_l2c_ = l2c;
+    lb_state_ = at::zeros({2 * memory + 3, ld_}, beta_.options());
+    lb_ring_ = at::zeros({4}, beta_.options().dtype(at::kInt));
+  }
+  // (state fp64 [2 memory + 3, ld], ring int32 [4]): what a checkpoint stores and a resume copies into
+  std::pair<Tensor, Tensor> lbfgs_state() const {
+    need(lb_memory_ > 0, "no lbfgs schedule");
+    return {lb_state_, lb_ring_};
+  }
+
   // --delay-on worker: virtual delays the collector applies to REMOTE messages (the worker ranks
   // are physically late themselves); default: the same table as the local messages.
   void set_remote_delays(const std::vector<double>& delays) {
@@ -577,7 +607,7 @@ class MasterPump {
         if (!graph) decode_round(i);
         char* g = ring_slot(G_, g_rows_, i);
         eh::LocalUpdate up;
-        if (fused_update_ && prox_.empty() && pc_damp_.empty() && launcher_->can_fuse_update() &&
+        if (fused_update_ && prox_.empty() && pc_damp_.empty() && !lb_memory_ && launcher_->can_fuse_update() &&
             local_update(i, useds[i - a], g, st + i + 1, &up)) {
           hcheck(launcher_->launch_update(beta_row(i), g, up, stream_), "local gradient + update");
           continue;
@@ -635,6 +665,7 @@ class MasterPump {
   std::string device_blocker(int a, int b) const {
     if (!prox_.empty()) return "proximal step after the update (L1 penalty)";
     if (!pc_damp_.empty()) return "preconditioned step (the update divides by the decoded curvature diagonal)";
+    if (lb_memory_) return "L-BFGS step (the update keeps a ring of pairs and runs as one workgroup)";
     if (blocks_) return "per-model update coefficients (multi-model run)";
     if (comm_) return "messages travel over " + comm_->kind() + " (the arbiter polls IPC counters)";
     if (remote_.empty() || arb_src_.empty()) return "no remote workers";
@@ -877,7 +908,13 @@ class MasterPump {
       else
         eh::set_block_coefs(bc, 1, ld_, d_, &decay_[i], &gm_[i], &l2_[i]);
     };
-    if (!pc_damp_.empty()) {  // the diagonal-Newton step
+    if (lb_memory_) {  // the quasi-Newton step
+      const eh::LbfgsCoefs lc{ld_, d_, lb_eta_[i], lb_gs_[i], lb_l2c_[i], lb_tau_, lb_memory_};
+      hcheck(eh::lbfgs_update_launch(a, acc_, acc_, beta_.data_ptr<double>(),
+                                     hist_.data_ptr<double>() + static_cast<int64_t>(i) * ld_, beta_row(i + 1),
+                                     lb_state_.data_ptr<double>(), lb_ring_.data_ptr<int>(), lc, stream_, stamp),
+             "lbfgs_update");
+    } else if (!pc_damp_.empty()) {  // the diagonal-Newton step
       const eh::PrecondCoefs pc{pc_ldx_, pc_dx_, pc_eta_[i], pc_gs_[i], pc_l2c_[i], pc_damp_[i], theta_[i], update_rule_};
       hcheck(eh::combine_update_precond_launch(a, acc_, acc_, beta_.data_ptr<double>(), u_.data_ptr<double>(),
                                                hist_.data_ptr<double>() + static_cast<int64_t>(i) * ld_,
@@ -1188,6 +1225,11 @@ class MasterPump {
   // set_precond_schedule: [R] each; pc_damp_ empty = no preconditioner
   int pc_ldx_ = 0, pc_dx_ = 0;
   std::vector<double> pc_eta_, pc_gs_, pc_l2c_, pc_damp_;
+  // set_lbfgs_schedule: [R] each; lb_memory_ 0 = no L-BFGS
+  int lb_memory_ = 0;
+  double lb_tau_ = 1.0;
+  std::vector<double> lb_eta_, lb_gs_, lb_l2c_;
+  Tensor lb_state_, lb_ring_;
   std::vector<double> prox_;  // set_prox_schedule: soft thresholds [R * max(1, blocks_)]; empty = no proximal step
   int repeat_ = 1;
   int update_rule_ = 0, stop_rule_ = 0, k_ = 0;
@@ -1247,6 +1289,8 @@ void bind_master_pump(py::module& m) {
       .def("set_block_schedule", &MasterPump::set_block_schedule)
       .def("set_prox_schedule", &MasterPump::set_prox_schedule)
       .def("set_precond_schedule", &MasterPump::set_precond_schedule)
+      .def("set_lbfgs_schedule", &MasterPump::set_lbfgs_schedule)
+      .def("lbfgs_state", &MasterPump::lbfgs_state)
       .def("set_decode", &MasterPump::set_decode)
       .def("add_table", &MasterPump::add_table)
       .def("begin", &MasterPump::begin, py::call_guard<py::gil_scoped_release>())

@@ -48,6 +48,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "step by it; --lr then multiplies a Newton-like step, so start near 1")
     g.add_argument("--precondition-damping", type=float, default=1e-8, metavar="DELTA",
                    help="--precondition diag: delta > 0 added to every diagonal entry (default 1e-8)")
+    g.add_argument("--lbfgs", type=int, default=0, metavar="M",
+                   help="limited-memory BFGS steps of the master with M in 1..7 pairs kept (0 = off): the direction is "
+                        "the two-loop recursion over the accepted (s, y) pairs, formed in one launch from a Gram matrix; "
+                        "--lr and its schedule give the GD step taken while no pair is held")
+    g.add_argument("--lbfgs-step", type=float, default=None, metavar="TAU",
+                   help="--lbfgs: beta -= TAU * p (default 1)")
     g.add_argument("--num-itrs", type=int, default=100)
     g.add_argument("--lr", type=float, default=10.0)
     g.add_argument("--lr-schedule", default="const", choices=["const", "invscaling", "exponential"],
@@ -149,6 +155,8 @@ def parse(argv: List[str]):
         return None, a
     (n_procs, n_rows, n_cols, input_dir, is_real, dataset, is_coded, n_stragglers, partitions, coded_ver,
      num_collect, add_delay, update_rule) = a.positional
+    if a.lbfgs_step is not None and not a.lbfgs:
+        raise ValueError("--lbfgs-step: needs --lbfgs M")
     cfg = RunConfig(int(n_procs), int(n_rows), int(n_cols), input_dir, int(is_real), dataset, int(is_coded),
                     int(n_stragglers), int(partitions), int(coded_ver), int(num_collect), int(add_delay),
                     update_rule, num_itrs=a.num_itrs, alpha=a.alpha, lr=a.lr,
@@ -165,7 +173,8 @@ def parse(argv: List[str]):
                     dedicated_master=a.dedicated_master, device_records=a.device_records,
                     sweep_alpha=a.alphas, sweep_lr=a.lrs, l1=a.l1, sweep_l1=a.l1s,
                     class_weight=a.class_weight, sample_weights=a.sample_weights, ovr=a.ovr, cv=a.cv,
-                    precondition=a.precondition, precondition_damping=a.precondition_damping)
+                    precondition=a.precondition, precondition_damping=a.precondition_damping,
+                    lbfgs=a.lbfgs, lbfgs_step=1.0 if a.lbfgs_step is None else a.lbfgs_step)
     return cfg, a
 
 

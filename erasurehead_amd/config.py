@@ -76,6 +76,10 @@ class RunConfig:
     # X (ops/precond.py); lr then multiplies a Newton-like step (values near 1).  damping: delta > 0, finite.
     precondition: str = "none"
     precondition_damping: float = 1e-8
+    # Limited-memory BFGS steps of the master (csrc/kernels/lbfgs.hip): lbfgs = M in 1..7 pairs (s, y) kept, 0 = off;
+    # beta -= lbfgs_step * p with p the two-loop direction; the run's GD step (lr, its schedule) while no pair is held
+    lbfgs: int = 0
+    lbfgs_step: float = 1.0
     # (alpha, lr) sweep: M = 2..8 models trained in one run from one pass over X per round (ops/multimodel.py).
     # The lists are zipped; an absent list or one of length 1 is broadcast (absent: the run's alpha / lr).
     sweep_alpha: Optional[List[float]] = None
@@ -167,6 +171,7 @@ class RunConfig:
         if self.cv is not None:
             self._check_cv()
         self._check_precondition()
+        self._check_lbfgs()
         if self.loss == "softmax":
             self.classes = 2 if self.classes is None else int(self.classes)
             if not 2 <= self.classes <= 8:
@@ -253,6 +258,34 @@ class RunConfig:
             raise ValueError("--precondition: bf16 storage is not supported (--precision fp64, fp32 or fp32x64)")
         if self.is_real and self.data != "synthetic":
             raise ValueError("--precondition: sparse data sources are not supported (dense partitions only)")
+
+    def _check_lbfgs(self) -> None:
+        """The limits of an L-BFGS run that the configuration alone decides, each a ValueError naming the flag."""
+        if isinstance(self.lbfgs, bool) or self.lbfgs != int(self.lbfgs):
+            raise ValueError(f"--lbfgs: the memory must be an integer in 1..7 (0 = off), got {self.lbfgs!r}")
+        self.lbfgs, self.lbfgs_step = int(self.lbfgs), float(self.lbfgs_step)
+        if not 0 <= self.lbfgs <= 7:
+            raise ValueError(f"--lbfgs: the memory must be in 1..7 (0 = off), got {self.lbfgs}")
+        if not (np.isfinite(self.lbfgs_step) and self.lbfgs_step > 0):
+            raise ValueError(f"--lbfgs-step: must be finite and > 0, got {self.lbfgs_step}")
+        if self.lbfgs == 0:
+            if self.lbfgs_step != 1.0:  # (the command line also refuses an explicit 1: cli.parse)
+                raise ValueError("--lbfgs-step: needs --lbfgs M")
+            return
+        if self.update_rule == "AGD":
+            raise ValueError("--lbfgs: the update rule must be GD (no momentum on a quasi-Newton step)")
+        if self.loss == "softmax":
+            raise ValueError("--lbfgs: not supported with --loss softmax (one model of a scalar loss)")
+        if self.ovr is not None:
+            raise ValueError("--lbfgs: cannot be combined with --ovr")
+        if self.cv is not None:
+            raise ValueError("--lbfgs: cannot be combined with --cv")
+        if self.sweep_alpha is not None or self.sweep_lr is not None or self.sweep_l1 is not None:
+            raise ValueError("--lbfgs: cannot be combined with a sweep (--alphas / --lrs / --l1s)")
+        if float(self.l1) != 0:
+            raise ValueError("--lbfgs: cannot be combined with --l1 (OWL-QN is not implemented)")
+        if self.precondition != "none":
+            raise ValueError("--lbfgs: cannot be combined with --precondition diag")
 
     def _sweep_lists(self) -> Optional[Tuple[List[float], List[float], List[float]]]:
         """([alpha_k], [lr_k], [l1_k]) of a sweep run, every list broadcast to the M models; None without a list."""

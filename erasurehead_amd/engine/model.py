@@ -29,13 +29,15 @@ from ..ops.ovr import OvrGradPlan
 from ..ops.precision import Precision
 from ..ops.precond import PrecondGradPlan
 from ..ops.softmax import SoftmaxGradPlan
-from ..ops.update import combine_update, combine_update_blocks, combine_update_precond, combine_update_prox
+from ..ops.update import (combine_update, combine_update_blocks, combine_update_precond, combine_update_prox,
+                          lbfgs_state, lbfgs_update)
 
 SQHINGE_PREFIX = "sqhinge_"  # result files of squared-hinge runs (next to the logistic names)
 SOFTMAX_PREFIX = "softmax_"
 OVR_PREFIX = "ovr_"  # result files of one-vs-rest runs (before sqhinge_)
 WEIGHTED_PREFIX = "weighted_"  # result files of runs with class / sample weights
 PRECOND_PREFIX = "precond_"  # result files of --precondition diag runs (before sqhinge_)
+LBFGS_PREFIX = "lbfgs_"  # result files of --lbfgs runs (before sqhinge_)
 
 
 def sweep_prefix(k: int) -> str:
@@ -69,6 +71,9 @@ class ModelSpec:
     # --precondition diag: "diag" and the damping delta > 0 of P = gs max(h, 0) + 2 alpha + delta; "none" / 0.0 without
     precondition: str = "none"
     damping: float = 0.0
+    # --lbfgs M: the pairs kept (0 = off) and the step tau of beta -= tau p; the model's layout is the single model's
+    lbfgs: int = 0
+    lbfgs_step: float = 1.0
 
     # ---------------------------------------------------------------- resolution and rejections
     @classmethod
@@ -126,6 +131,12 @@ class ModelSpec:
                 raise ValueError("--precondition: class / sample weights are not supported")
             kind = "precond"
             extra = dict(precondition=str(cfg.precondition), damping=float(cfg.precondition_damping))
+        if cfg.lbfgs:  # (the config rejected what it can see; these need the resolved run)
+            if kind != "single":
+                raise ValueError(f"--lbfgs: not supported with a {kind} model (one model of a scalar loss)")
+            if getattr(scheme, "fixed_agd", False):
+                raise ValueError("--lbfgs: this scheme always updates by AGD; the update rule must be GD")
+            extra = dict(lbfgs=int(cfg.lbfgs), lbfgs_step=float(cfg.lbfgs_step))
         d_x = int(cfg.n_cols)
         spec = cls(kind, loss, weighted, classes, models, d_x, prec.ld(d_x), float(cfg.l1),
                    [a for a, _ in sweep] if sweep else None, [x for _, x in sweep] if sweep else None,
@@ -319,9 +330,10 @@ class ModelSpec:
 
     def result_names(self, names: Dict[str, str], model_prefix: str = "") -> Dict[str, str]:
         """The scheme's result names under the run's prefixes: ``sweep{k}_`` / ``cv{k}_`` first, then ``softmax_`` /
-        ``ovr_``, ``weighted_``, ``precond_``, ``sqhinge_``."""
+        ``ovr_``, ``weighted_``, ``precond_``, ``lbfgs_``, ``sqhinge_``."""
         p = model_prefix + {"softmax": SOFTMAX_PREFIX, "ovr": OVR_PREFIX}.get(self.kind, "")
         p += (WEIGHTED_PREFIX if self.weighted else "") + (PRECOND_PREFIX if self.kind == "precond" else "")
+        p += LBFGS_PREFIX if self.lbfgs else ""
         p += (SQHINGE_PREFIX if base_kind(self.loss) == SQUARED_HINGE else "")
         return {k: p + v for k, v in names.items()}
 
@@ -337,6 +349,8 @@ class ModelSpec:
             rep.update(cv=self.cv, fold_rows=list(self.fold_rows))
         if self.kind == "precond":
             rep.update(precondition=self.precondition, damping=self.damping)
+        if self.lbfgs:
+            rep.update(lbfgs=self.lbfgs, lbfgs_step=self.lbfgs_step)
         rep.update(l1=list(self.sweep_l1) if self.kind == "sweep" else self.l1, prox=bool(self.prox),
                    weighted=bool(self.weighted))
         return rep
@@ -358,6 +372,9 @@ class ModelSpec:
         if self.kind == "precond":
             state["precondition"] = self.precondition
             state["precondition_damping"] = float(self.damping)
+        if self.lbfgs:  # (the trainer adds the state itself: lbfgs_state, lbfgs_ring)
+            state["lbfgs"] = int(self.lbfgs)
+            state["lbfgs_step"] = float(self.lbfgs_step)
         return state
 
     def check_checkpoint(self, st, path: str, weight_spec) -> None:
@@ -391,6 +408,14 @@ class ModelSpec:
             raise ValueError(f"checkpoint {path} was written by a run with precondition = {have_pc[0]}, damping = "
                              f"{have_pc[1]:g}; this run has precondition = {self.precondition}, damping = "
                              f"{self.damping:g} (--precondition / --precondition-damping)")
+        have_lb = (int(st.get("lbfgs", 0)), float(st.get("lbfgs_step", 1.0)))
+        if have_lb != (self.lbfgs, float(self.lbfgs_step)):
+            raise ValueError(f"checkpoint {path} was written by a run with lbfgs = {have_lb[0]}, lbfgs_step = "
+                             f"{have_lb[1]:g}; this run has lbfgs = {self.lbfgs}, lbfgs_step = {self.lbfgs_step:g} "
+                             f"(--lbfgs / --lbfgs-step)")
+        if self.lbfgs and (st.get("lbfgs_state") is None or st.get("lbfgs_ring") is None or
+                           tuple(st["lbfgs_state"].shape) != (2 * self.lbfgs + 3, self.ld)):
+            raise ValueError(f"checkpoint {path} lacks the L-BFGS state of a --lbfgs {self.lbfgs} run")
         have_w = st.get("weights")
         if have_w != weight_spec:
             raise ValueError(f"checkpoint {path} was written by a run with weights = {have_w}; this run has "
@@ -418,6 +443,11 @@ class UpdateSchedule:
     # block of the [2][ld_x] vector; None without
     precond: Optional[np.ndarray] = None
     precond_block: Tuple[int, int] = (0, 0)
+    # --lbfgs M: [3, R] eta, gs, l2c of the quasi-Newton step (UpdateRule.lbfgs_coeffs), (M, tau), and for the Python
+    # round loop the (state, ring) tensors of ops/update.py lbfgs_state that the rounds advance; None without
+    lbfgs: Optional[np.ndarray] = None
+    lbfgs_cfg: Tuple[int, float] = (0, 1.0)
+    lbfgs_state: Optional[tuple] = None
 
     @classmethod
     def build(cls, rule: UpdateRule, rounds: int, eta, sweep_etas, spec: ModelSpec) -> "UpdateSchedule":
@@ -450,13 +480,21 @@ class UpdateSchedule:
             precond = np.array([[c[k] for c in pco] for k in range(3)] + [[spec.damping] * R],
                                dtype=np.float64).reshape(4, R)
             pblock = (spec.ld_x, spec.d_x)
-        return cls(decay, gm, l2, thr, theta, code, *block, single, precond, pblock)
+        lb = None
+        if spec.lbfgs:
+            lb = np.array([rule.lbfgs_coeffs(i, float(eta[i])) for i in range(R)], dtype=np.float64).reshape(R, 3).T
+        return cls(decay, gm, l2, thr, theta, code, *block, single, precond, pblock, lb, (spec.lbfgs, spec.lbfgs_step))
 
     def apply(self, i: int, msgs, coefs, beta, u, hist, beta_w) -> None:
         """Round i's combine + update (ops/update.py): with a threshold the proximal form (a single model as one
         block), a sweep without one the blocked form, anything else the plain one."""
         theta = float(self.theta[i])
-        if self.precond is not None:
+        if self.lbfgs is not None:
+            if self.lbfgs_state is None:
+                self.lbfgs_state = lbfgs_state(self.lbfgs_cfg[0], beta.numel(), beta.device)
+            lbfgs_update(msgs, coefs, beta, *self.lbfgs_state, self.block_d, *(float(x) for x in self.lbfgs[:, i]),
+                         self.lbfgs_cfg[1], hist=hist, beta_w=beta_w)
+        elif self.precond is not None:
             combine_update_precond(msgs, coefs, beta, u, *self.precond_block, *(float(x) for x in self.precond[:, i]),
                                    theta, self.code, hist=hist, beta_w=beta_w)
         elif self.thr is not None:
@@ -482,3 +520,5 @@ class UpdateSchedule:
             pump.set_prox_schedule(self.thr.ravel().tolist())
         if self.precond is not None:  # the rounds then stay off both fused update paths, like a proximal run's
             pump.set_precond_schedule(*self.precond_block, *(x.tolist() for x in self.precond))
+        if self.lbfgs is not None:  # the pump owns the state (pump.lbfgs_state()); off both fused update paths too
+            pump.set_lbfgs_schedule(self.lbfgs_cfg[0], self.lbfgs_cfg[1], *(x.tolist() for x in self.lbfgs))

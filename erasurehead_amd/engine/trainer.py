@@ -56,6 +56,7 @@ from ..models.losses import UpdateRule
 from ..ops.blockplan import BlockGradPlan
 from ..ops.grad import SharedGradPlan, SparseGradPlan
 from ..ops.precision import get_precision
+from ..ops.update import lbfgs_state
 from ..parallel.collector import ArrivalCollector
 from ..parallel.dist import DistEnv
 from ..parallel.placement import make_shards, place_spread, place_units
@@ -113,6 +114,8 @@ def _mean_us(ms, a0: int = 0) -> Optional[float]:
 
 
 class Trainer:
+    lbfgs_state = None  # the master of a --lbfgs run: (state, ring) of ops/update.py lbfgs_state
+
     def __init__(self, cfg: RunConfig, env: Optional[DistEnv] = None, source: Optional[DataSource] = None,
                  scheme: Optional[Scheme] = None):
         self.cfg = cfg
@@ -353,6 +356,8 @@ class Trainer:
             self.Rbuf = self.tx.make_rbuf() if self.tx is not None else None
             self.beta = torch.zeros(ld, dtype=torch.float64, device=dev)
             self.u = torch.zeros(ld, dtype=torch.float64, device=dev)
+            # --lbfgs: the ring of pairs and the previous round's beta / gradient (ops/update.py lbfgs_state)
+            self.lbfgs_state = lbfgs_state(self.model.lbfgs, ld, dev) if self.model.lbfgs else None
             self.hist = torch.zeros((R, ld), dtype=torch.float64, device=dev)
             self.beta_in = torch.zeros((R + 1, ld), dtype=acc, device=dev)
             self.loc_index = {(m.worker, m.part, m.shard): j for j, m in enumerate(self.local_msgs)}
@@ -428,6 +433,8 @@ class Trainer:
         packed = self.model.beta0(self.scheme.init_zero, self.cfg.seed)  # [ld], padding columns zero
         self.beta.copy_(torch.from_numpy(packed).to(self.beta.device))
         self.u.zero_()
+        for t in self.lbfgs_state or ():  # a second run() starts without pairs; a resume overwrites it, as it does u
+            t.zero_()
         self.beta_in[0].copy_(self.beta.to(self.beta_in.dtype))
         self.beta0 = packed[: self.d]
 
@@ -769,7 +776,9 @@ class Trainer:
     def _update_schedule(self) -> UpdateSchedule:
         """The run's per-round update coefficients (engine/model.py), for either master loop."""
         cfg = self.cfg
-        return UpdateSchedule.build(self.update, cfg.num_itrs, cfg.eta(), cfg.sweep_etas(), self.model)
+        sched = UpdateSchedule.build(self.update, cfg.num_itrs, cfg.eta(), cfg.sweep_etas(), self.model)
+        sched.lbfgs_state = self.lbfgs_state  # the Python loop's rounds advance the trainer's own state
+        return sched
 
     def _result(self, timeset, worker_timeset, loop_time, total, timeouts, arrivals_log, timed_start, t_timed0,
                 t_timed1) -> TrainResult:
@@ -875,6 +884,11 @@ class Trainer:
         delay_table = self.delay_table()
         self._update_schedule().install(pump, [float(x) for x in delay_table.ravel()], self.rule_kind, self.rule_k,
                                         bool(self.drain))
+        if self.lbfgs_state is not None:  # the pump owns the state from here on: hand it what a resume restored
+            owned = pump.lbfgs_state()
+            for dst, src in zip(owned, self.lbfgs_state):
+                dst.copy_(src)
+            self.lbfgs_state = tuple(owned)
         if self.physical:  # remote messages are really late: the collector applies no virtual delay to them
             pump.set_remote_delays([float(x) for x in self._remote_delays(delay_table).ravel()])
         if self._clocks and tx is not None and (self.physical or cfg.device_records):
@@ -1253,6 +1267,9 @@ class Trainer:
         self.u.copy_(st["u"].to(dev))
         self.hist[:nxt].copy_(st["hist"].to(dev))
         self.beta_in[nxt].copy_(self.beta.to(self.beta_in.dtype))
+        if self.lbfgs_state is not None:
+            self.lbfgs_state[0].copy_(st["lbfgs_state"].to(dev))
+            self.lbfgs_state[1].copy_(st["lbfgs_ring"].to(dev))
         self._restored = {"timeset": st["timeset"].numpy(), "worker_timeset": st["worker_timeset"].numpy()}
         return nxt
 
@@ -1268,6 +1285,8 @@ class Trainer:
                  "hist": self.hist[:next_round].cpu(), "timeset": torch.from_numpy(timeset[:next_round].copy()),
                  "worker_timeset": torch.from_numpy(worker_timeset[:next_round].copy()), "scheme": self.key}
         state.update(self.model.checkpoint_state(self.weight_spec))
+        if self.lbfgs_state is not None:
+            state["lbfgs_state"], state["lbfgs_ring"] = (t.cpu() for t in self.lbfgs_state)
         if getattr(self.scheme, "B", None) is not None:
             state["B"] = torch.from_numpy(np.ascontiguousarray(self.scheme.B, dtype=np.float64))
         tmp = path + ".tmp"

@@ -378,6 +378,18 @@ def soft_threshold(x, t):
 
 
 @dataclass
+class LbfgsState:
+    """What the oracle UpdateRule.step_lbfgs remembers between rounds (the engines keep ops/update.py lbfgs_state):
+    at most `memory` accepted pairs (s, y), oldest first, and the previous round's beta and gradient (None before the
+    first round)."""
+
+    memory: int
+    pairs: list = dataclasses.field(default_factory=list)
+    beta_prev: Optional[np.ndarray] = None
+    g_prev: Optional[np.ndarray] = None
+
+
+@dataclass
 class UpdateRule:
     """GD / AGD with the reference's constants (alpha = 1/n_rows, eta schedule), and optionally the proximal
     step of an L1 penalty l1 * ||beta||_1 (lasso / elastic net) after every update."""
@@ -433,6 +445,44 @@ class UpdateRule:
             betatemp = (1 - theta) * beta + theta * u - step
             u[:] = beta + (betatemp - beta) * (1 / theta)
             beta[:] = betatemp
+
+    def lbfgs_coeffs(self, i: int, eta: float) -> Tuple[float, float, float]:
+        """(eta, gs, l2c) of round i's L-BFGS step: the gradient is G = gs g + l2c beta, as precond_coeffs'."""
+        if self.rule != "GD":
+            raise ValueError("--lbfgs: the update rule must be GD")
+        return float(eta), self.grad_scale / self.n_samples, 2.0 * self.alpha
+
+    def step_lbfgs(self, i: int, eta: float, beta: np.ndarray, g: np.ndarray, state: "LbfgsState", tau: float) -> int:
+        """In-place limited-memory BFGS update from the decoded message sum g: the textbook two-loop recursion over
+        full-length vectors.  An oracle only: the engines, CPU and GPU, step through ops/update.py lbfgs_update, which
+        reads the same dot products off a Gram matrix; this second formulation is what replays hold them to.  Returns
+        the step's mode: 0 quasi-Newton, 1 GD (no pair held), 2 GD and the ring emptied."""
+        eta, gs, l2c = self.lbfgs_coeffs(i, eta)
+        b = beta.copy()
+        with np.errstate(all="ignore"):
+            G = gs * g + l2c * b
+            if state.beta_prev is not None:
+                s, y = b - state.beta_prev, G - state.g_prev
+                sy, ss, yy = s.dot(y), s.dot(s), y.dot(y)
+                if np.isfinite([sy, ss, yy]).all() and sy > 1e-8 * np.sqrt(ss * yy):
+                    state.pairs = (state.pairs + [(s, y)])[-state.memory:]
+            mode, q = 1, G
+            if state.pairs:
+                q, a = G.copy(), []
+                for s, y in reversed(state.pairs):
+                    a.append(s.dot(q) / s.dot(y))
+                    q -= a[-1] * y
+                s, y = state.pairs[-1]
+                q *= s.dot(y) / y.dot(y)
+                for (s, y), aj in zip(state.pairs, reversed(a)):
+                    q += (aj - y.dot(q) / s.dot(y)) * s
+                gp = G.dot(q)
+                mode = 0 if np.isfinite(gp) and gp > 0 else 2
+            if mode == 2:
+                state.pairs = []
+            beta -= tau * q if mode == 0 else eta * G
+        state.beta_prev, state.g_prev = b, G
+        return mode
 
     def apply(self, i: int, eta: float, beta: np.ndarray, u: np.ndarray, g: np.ndarray) -> None:
         """In-place host update (oracle of the combine_update kernel; with l1 > 0 of combine_update_prox: the new

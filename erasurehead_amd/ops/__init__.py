@@ -7,4 +7,5 @@ from .ovr import OvrGradPlan
 from .cv import CvGradPlan
 from .precond import PrecondGradPlan
 from .precision import PRECISIONS, Precision, get_precision
-from .update import combine_update, combine_update_blocks, combine_update_precond, combine_update_prox
+from .update import (combine_update, combine_update_blocks, combine_update_precond, combine_update_prox, lbfgs_pairs,
+                     lbfgs_state, lbfgs_update)

@@ -6,8 +6,9 @@ betaset history row and the worker-precision copy of the new beta.
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from .._ext import native
@@ -90,6 +91,100 @@ def combine_update_precond(msgs: Sequence[torch.Tensor], coefs: Sequence[float],
     if beta_w is not None:
         beta_w.zero_()
         beta_w[:d_x] = nb.to(beta_w.dtype)
+
+
+LBFGS_MAX_MEMORY = 7  # 2 * 7 + 1 columns of V = [s_1..s_k, y_1..y_k, G] fill one 16-wide MFMA tile (lbfgs.hip)
+
+
+def lbfgs_state(memory: int, ld: int, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A fresh L-BFGS state for a model of ``ld`` elements: ``state`` fp64 ``[2 * memory + 3, ld]`` (the ring's s rows,
+    its y rows, beta_prev, G_prev and a row that keeps the last step's direction) and ``ring`` int32 ``[4]`` (head,
+    count, 1 once a round has been seen, the last step's mode: 0 quasi-Newton, 1 GD without a pair, 2 GD and the ring
+    emptied).  ``lbfgs_update`` advances both in place."""
+    memory = int(memory)
+    if not 1 <= memory <= LBFGS_MAX_MEMORY:
+        raise ValueError(f"--lbfgs: the memory must be in 1..{LBFGS_MAX_MEMORY}, got {memory}")
+    return (torch.zeros((2 * memory + 3, int(ld)), dtype=torch.float64, device=device),
+            torch.zeros(4, dtype=torch.int32, device=device))
+
+
+def lbfgs_pairs(state: torch.Tensor, ring: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(S, Y) of the pairs the state holds, ``[count, ld]`` each, oldest first."""
+    memory = (state.shape[0] - 3) // 2
+    head, count = (int(x) for x in ring[:2].tolist())
+    rows = [(head + j) % memory for j in range(count)]
+    return state[rows], state[[memory + r for r in rows]]
+
+
+def lbfgs_update(msgs: Sequence[torch.Tensor], coefs: Sequence[float], beta: torch.Tensor, state: torch.Tensor,
+                 ring: torch.Tensor, d: int, eta: float, gs: float, l2c: float, tau: float,
+                 hist: Optional[torch.Tensor] = None, beta_w: Optional[torch.Tensor] = None,
+                 gate: Optional[torch.Tensor] = None) -> None:
+    """One limited-memory BFGS combine + update on the state of :func:`lbfgs_state` (csrc/kernels/lbfgs.hip): g = sum_m
+    coef_m msg_m, ``G = gs g + l2c beta``, the candidate pair ``(beta - beta_prev, G - G_prev)`` enters the ring iff
+    ``s.y > 1e-8 sqrt(s.s y.y)`` with finite dots, and the step is ``beta -= tau p`` with p the two-loop recursion over
+    the held pairs -- ``beta -= eta G`` while none is held, or, with the ring emptied, when ``G.p`` is not finite and
+    > 0.  Native on GPU tensors; on CPU tensors a NumPy twin of the same Gram-space algorithm (every dot product read
+    off ``V^T V``, the recursion on coefficient vectors)."""
+    memory, ld, d, tau = (int(state.shape[0]) - 3) // 2, int(beta.numel()), int(d), float(tau)
+    if state.dim() != 2 or state.shape[0] != 2 * memory + 3 or not 1 <= memory <= LBFGS_MAX_MEMORY or \
+            state.shape[1] != ld or state.dtype != torch.float64 or ring.numel() != 4 or ring.dtype != torch.int32:
+        raise ValueError(f"lbfgs_update: state must be float64 [2 * memory + 3, {ld}] with memory in 1.."
+                         f"{LBFGS_MAX_MEMORY} and ring int32 [4], got {list(state.shape)} and {list(ring.shape)}")
+    if not 1 <= d <= ld:
+        raise ValueError(f"lbfgs_update: d must be in 1..{ld}, got {d}")
+    if not (tau > 0.0 and tau != float("inf")):
+        raise ValueError(f"lbfgs_update: the step must be finite and > 0, got {tau}")
+    if beta.is_cuda:
+        C = native()
+        if len(msgs) > C.MAX_MSGS:
+            raise ValueError(f"at most {C.MAX_MSGS} messages per combine")
+        C.lbfgs_update(list(msgs), [float(c) for c in coefs], beta, hist, beta_w, state, ring, memory, d, float(eta),
+                       float(gs), float(l2c), tau, gate)
+        return
+    if gate is not None and int(gate.reshape(-1)[0]) != 0:
+        return
+    st, rg, b = state.numpy(), ring.numpy(), beta.numpy()[:d].copy()
+    g = np.zeros(d)
+    for m, c in zip(msgs, coefs):
+        g += float(c) * m[:d].double().numpy()
+    G = gs * g + l2c * b
+    head, count, started = int(rg[0]), int(rg[1]), bool(rg[2])
+    with np.errstate(all="ignore"):
+        if started:
+            s, y = b - st[2 * memory, :d], G - st[2 * memory + 1, :d]
+            sy, ss, yy = s.dot(y), s.dot(s), y.dot(y)
+            if np.isfinite([sy, ss, yy]).all() and sy > 1e-8 * np.sqrt(ss * yy):
+                slot = (head + count) % memory if count < memory else head
+                st[slot, :d], st[memory + slot, :d] = s, y
+                head, count = (head, count + 1) if count < memory else ((head + 1) % memory, count)
+        mode, p = 1, G
+        if count:
+            k, rows = count, [(head + j) % memory for j in range(count)]
+            V = np.stack([st[r, :d] for r in rows] + [st[memory + r, :d] for r in rows] + [G], axis=1)  # [d, 2k + 1]
+            Wg, c = V.T.dot(V), np.zeros(2 * k + 1)
+            c[2 * k] = 1.0
+            a = np.zeros(k)
+            for j in range(k - 1, -1, -1):
+                a[j] = Wg[j].dot(c) / Wg[j, k + j]
+                c[k + j] -= a[j]
+            c *= Wg[k - 1, 2 * k - 1] / Wg[2 * k - 1, 2 * k - 1]
+            for j in range(k):
+                c[j] += a[j] - Wg[k + j].dot(c) / Wg[j, k + j]
+            gp = Wg[2 * k].dot(c)
+            mode = 0 if np.isfinite(gp) and gp > 0 else 2
+            if mode == 0:
+                p = V.dot(c)
+        nb = b - tau * p if mode == 0 else b - eta * G
+    st[2 * memory, :d], st[2 * memory + 1, :d], st[2 * memory + 2, :d] = b, G, p
+    rg[:] = (0 if mode == 2 else head, 0 if mode == 2 else count, 1, mode)
+    new = torch.from_numpy(nb)
+    beta[:d] = new
+    if hist is not None:
+        hist[:d] = new
+    if beta_w is not None:
+        beta_w.zero_()
+        beta_w[:d] = new.to(beta_w.dtype)
 
 
 def _update_blocked(name, msgs, coefs, beta, u, block_ld, d_x, decay, gm, l2, thr, theta, rule, hist, beta_w,
