@@ -213,6 +213,18 @@ hipError_t eval_gemm_loss_launch(int x_dtype, int loss_kind, const void* X, long
                                  long long n, int d, const void* y, const void* B, int ldb,
                                  int R, double* loss, void* P, hipStream_t st);
 
+// ---- multi-class evaluation: loss and accuracy in the GEMM epilogue (eval_classes.hip) -------
+// loss[r] += sum over the n rows of the row's loss under the C models B[r * C .. r * C + C - 1], hits[r] += the rows
+// whose label is the first argmax of their C logits; no logit is stored.  x_dtype: storage code 0, 1 or 3 (y and B in
+// its accumulator type, y the class indices); mode 0 softmax cross-entropy, 1 / 2 one-vs-rest logistic / squared
+// hinge; B [R * C, ldb] round-major; 2 <= C <= 8; d <= ldx, ldb.  Anything else is hipErrorInvalidValue and launches
+// nothing; n == 0 or R == 0 launches nothing.  A workgroup covers kEvalClassRows rows and kEvalClassCols / CP rounds,
+// CP = C rounded up to 2, 4 or 8.
+constexpr int kEvalClassRows = 128;
+constexpr int kEvalClassCols = 112;
+hipError_t eval_classes_launch(int x_dtype, int mode, const void* X, long long ldx, long long n, int d, const void* y,
+                               const void* B, int ldb, int R, int C, double* loss, double* hits, hipStream_t st);
+
 // ---- post-hoc evaluation over CSR / one-hot rows (eval_sparse.hip) ---------------------------
 // Bt: betas transposed [ld, R] (R <= 256); vals == nullptr: pattern-only; dtype 0 fp64, 1 fp32
 hipError_t eval_csr_loss_launch(int dtype, int loss_kind, const long long* row_ptr, const int* col, const void* vals,

@@ -45,7 +45,8 @@ import torch
 
 from ..data import io as dio
 from ..models.losses import LOGISTIC
-from ..ops.eval import auc_columns, loss_sums, predictions, predictions_and_loss, sign_labels
+from ..ops.eval import (CLASS_OVR_LOGISTIC, CLASS_OVR_SQUARED_HINGE, CLASS_SOFTMAX, auc_columns, class_loss_sums,
+                        loss_sums, predictions, predictions_and_loss, sign_labels)
 from ..utils import report
 from .trainer import TrainResult, Trainer
 
@@ -147,7 +148,18 @@ def _train_chunks(trainer: Trainer, parts, prec, dev):
         yield resident[p]
 
 
-def _class_sums(X, y, B, classes: int, d_x: int, row_loss):
+def _class_sums(X, y, B, classes: int, d_x: int, row_loss, mode: int, acc=None, fused: bool = True):
+    """(loss sums [R], correct counts [R]) of the rows X, y (class indices) for the models B [R * classes, ld_x].  Dense
+    fp64 / fp32 rows on the GPU: the evaluation GEMM with loss ``mode`` and the accuracy in its epilogue
+    (ops/eval.class_loss_sums; ``acc``: the run's precision); CPU tensors, sparse sources and ``fused=False`` (what the
+    GPU path is tested and timed against): :func:`_class_sums_torch` with ``row_loss``."""
+    if fused and isinstance(X, torch.Tensor) and X.layout == torch.strided and X.is_cuda \
+            and X.dtype in (torch.float64, torch.float32):
+        return class_loss_sums(X, y, B, classes, d_x, mode, acc)
+    return _class_sums_torch(X, y, B, classes, d_x, row_loss)
+
+
+def _class_sums_torch(X, y, B, classes: int, d_x: int, row_loss):
     """(loss sums [R], correct counts [R]) of the rows X, y (class indices) for the models B [R * classes, ld_x]:
     scores from the prediction GEMM (ops/eval.predictions), rounds chunked so the scores held at once stay bounded;
     row_loss(Z [n, r, classes], y [n]) gives a chunk's loss sums [r]."""
@@ -164,15 +176,15 @@ def _class_sums(X, y, B, classes: int, d_x: int, row_loss):
     return tot.numpy(), hit.numpy()
 
 
-def _softmax_sums(X, y, B, spec):
+def _softmax_sums(X, y, B, spec, acc=None, fused: bool = True):
     """Cross-entropy logsumexp(z) - z_y."""
     def ce(Z, yl):
         zy = Z.gather(2, yl[:, None, None].expand(Z.shape[0], Z.shape[1], 1))[:, :, 0]
         return (torch.logsumexp(Z, dim=2) - zy).sum(0)
-    return _class_sums(X, y, B, spec.classes, spec.d_x, ce)
+    return _class_sums(X, y, B, spec.classes, spec.d_x, ce, CLASS_SOFTMAX, acc, fused)
 
 
-def _ovr_sums(X, y, B, spec):
+def _ovr_sums(X, y, B, spec, acc=None, fused: bool = True):
     """Sum over classes of l(y_k z_k), l the run's logistic or squared-hinge loss."""
     def loss(Z, yl):
         own = yl[:, None, None] == torch.arange(spec.classes, device=Z.device)[None, None, :]
@@ -182,7 +194,8 @@ def _ovr_sums(X, y, B, spec):
         else:
             v = torch.clamp(1.0 + m, min=0) ** 2
         return v.sum(dim=(0, 2))
-    return _class_sums(X, y, B, spec.classes, spec.d_x, loss)
+    return _class_sums(X, y, B, spec.classes, spec.d_x, loss,
+                       CLASS_OVR_LOGISTIC if spec.loss == LOGISTIC else CLASS_OVR_SQUARED_HINGE, acc, fused)
 
 
 _CLASS_SUMS = {"softmax": _softmax_sums, "ovr": _ovr_sums}
@@ -199,11 +212,11 @@ def _evaluate_classes(trainer: Trainer, res: TrainResult, log, write: bool) -> E
         log(report.total_time_line(res.total_time))
     tr_sum, n_train = np.zeros(R), 0
     for X, y in _train_chunks(trainer, parts, prec, dev):
-        s, _ = sums(X, y, B, spec)
+        s, _ = sums(X, y, B, spec, prec)
         tr_sum += s
         n_train += X.shape[0]
     Xt, yt = trainer.source.test(prec, dev)
-    te_sum, hits = sums(Xt, yt, B, spec)
+    te_sum, hits = sums(Xt, yt, B, spec, prec)
     n_test = Xt.shape[0]
     training_loss = tr_sum / max(1, n_train)
     testing_loss = te_sum / max(1, n_test)

@@ -161,6 +161,27 @@ def predictions_and_loss(X, y: torch.Tensor, B: torch.Tensor, d: int, kind: int,
     return P, _loss_torch(kind, y.to(P.device), P).double().cpu().numpy()
 
 
+# what class_loss_sums scores (csrc/kernels/eval_classes.hip): softmax cross-entropy, or the one-vs-rest sum over the
+# classes of the binary logistic / squared-hinge loss
+CLASS_SOFTMAX, CLASS_OVR_LOGISTIC, CLASS_OVR_SQUARED_HINGE = 0, 1, 2
+
+
+def class_loss_sums(X: torch.Tensor, y: torch.Tensor, B: torch.Tensor, classes: int, d: int, mode: int,
+                    acc=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(loss sums [R], correct counts [R]) over the rows of a dense GPU X with class indices y, for the R models of
+    B [R * classes, >= d] (round-major, the class inside: ModelSpec.rows): one MFMA GEMM whose epilogue turns every
+    (row, round) group of ``classes`` logits into the row's loss and whether its first argmax is the label, so the
+    logits never reach memory.  The accumulator follows :func:`_dense_acc`; a label that is no class index makes the
+    loss NaN in every round and counts as a miss."""
+    a = _dense_acc(X, acc)
+    R = B.shape[0] // classes
+    loss = torch.zeros(R, dtype=torch.float64, device=X.device)
+    hits = torch.zeros(R, dtype=torch.float64, device=X.device)
+    native().eval_class_loss(mode, classes, X, X.shape[0], d, y.to(device=X.device, dtype=a).contiguous(),
+                             B.to(device=X.device, dtype=a).contiguous(), loss, hits)
+    return loss.cpu().numpy(), hits.cpu().numpy()
+
+
 def loss_sums(chunks: Iterable[Tuple[object, torch.Tensor]], B: torch.Tensor, d: int, kind: int,
               acc=None) -> Tuple[np.ndarray, int]:
     """Sum over all chunk rows of the per-row loss for every beta row of B -> ([R], n)."""
