@@ -194,6 +194,12 @@ hipError_t grad_folds_launch(int dtype, int loss, int folds, const void* segs, c
 hipError_t grad_curv_launch(int dtype, int loss, const void* segs, const void* tasks, int ntasks,
                             const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb, int d_x,
                             int ld_x, hipStream_t st, const int* gate = nullptr);
+// Gradient and Hessian-vector product of ONE scalar-loss model (grad_hvp.hip; --newton-cg J): beta and every Gb row
+// are [2][ld_x], beta block 0 the model and block 1 the direction v; Gb[p] block 0 = sum r_i x_i and block 1 =
+// sum l''(z_i) (x_i . v) x_i over partition p (exact zeros where v is).  dtype and loss as for grad_curv_launch.
+hipError_t grad_hvp_launch(int dtype, int loss, const void* segs, const void* tasks, int ntasks,
+                           const int* part_task_begin, int nparts, const void* beta, void* slab, void* Gb, int d_x,
+                           int ld_x, hipStream_t st, const int* gate = nullptr);
 // What grad_blocks.h answers for rows of `rowbytes` bytes and a model of `blocks` blocks: blocks_stage_rows and
 // blocks_wpg themselves (the tests hold the Python mirrors in ops/blockplan.py to them).
 void blocks_geometry(int rowbytes, int blocks, int* stage_rows, int* wpg);
@@ -339,6 +345,38 @@ struct LbfgsCoefs {
 hipError_t lbfgs_update_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* hist,
                                void* beta_w, double* state, int* ring, const LbfgsCoefs lc, hipStream_t st,
                                long long* stamp = nullptr, const int* gate = nullptr);
+// One round of truncated Newton (Newton-CG) on ONE model of a scalar loss (newton_cg.hip; --newton-cg J): one launch
+// of one workgroup.  beta, every message and beta_w are [2][ld_x]; block 0 of the messages decodes to g and block 1 to
+// u = (loss Hessian) dir with combine_update_precond's fma chain, G = gs g + l2c beta and H dir = gs u + l2c dir.  A
+// gradient round starts linear CG on H x = -G and sends [beta ; dir]; a CG round takes one CG step and either sends
+// the next direction or ends the outer iteration with beta' = beta + tau x and sends [beta' ; 0] (newton_cg.hip has
+// the recurrences and every branch).  hist takes [beta' ; 0] (beta itself while CG rounds run), beta_w the wire
+// model; block 1 of beta is not touched.  Everything the method remembers lives on the device and the kernel itself
+// advances it:
+//   state [5][ld_x] fp64: x, rres, dir, G0 and a scratch row (H dir between the passes of a CG round)
+//   scal  [2] fp64: rs = rres . rres, g0norm2 = G0 . G0
+//   phase [4] int32: phase (0 gradient round next, 1 CG round next), CG steps taken in this outer iteration, the last
+//         round's mode (kNewton* below), outer iterations finished
+// A fresh run starts from zeros.  J outside 1..kNewtonMaxInner, d_x outside 1..ld_x, a xi or tau that is not finite
+// and > 0, or an unknown dtype is hipErrorInvalidValue and nothing is launched.  gate: common.h gate_closed.
+constexpr int kNewtonMaxInner = 32;
+enum NewtonMode : int {
+  kNewtonStart = 0,          // gradient round: CG started, beta unchanged
+  kNewtonContinue = 1,       // CG step taken, the next direction sent
+  kNewtonStepTolerance = 2,  // CG step taken, rs' <= xi^2 g0norm2: beta += tau x
+  kNewtonStepCap = 3,        // CG step taken, the inner count reached J: beta += tau x
+  kNewtonStepCurvature = 4,  // kappa <= 0 (or not finite) after at least one CG step: beta += tau x with the x held
+  kNewtonGdCurvature = 5,    // kappa <= 0 (or not finite) on the first CG round: beta -= eta G0
+  kNewtonGdGradient = 6,     // gradient round with rs 0 or not finite: beta -= eta G
+};
+struct NewtonCoefs {
+  int ld_x, d_x;
+  double eta, gs, l2c, xi, tau;
+  int J;
+};
+hipError_t newton_cg_update_launch(const CombineArgs& args, int msg_dtype, int w_dtype, double* beta, double* hist,
+                                   void* beta_w, double* state, double* scal, int* phase, const NewtonCoefs nc,
+                                   hipStream_t st, long long* stamp = nullptr, const int* gate = nullptr);
 // one device timestamp (wall_clock64, hipDeviceAttributeWallClockRate kHz) into *out
 hipError_t stamp_launch(long long* out, hipStream_t st);
 

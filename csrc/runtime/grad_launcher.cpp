@@ -164,6 +164,15 @@ std::shared_ptr<GradLauncher> make_precond(int64_t dtype, int64_t loss, const Te
   return make_blocked(7, "preconditioned", "blocks", dtype, loss, 2, segs, tasks, slab, part_task_begin, d_x, ld_x);
 }
 
+// kind 8: one model of the scalar loss `loss` with a Hessian-vector product, blocks = 2: the model is [beta ; v] and
+// a row [gradient ; H v] (ops/hvp.py, kernels/grad_hvp.hip).  Like kind 7 it fuses neither the put nor the update.
+std::shared_ptr<GradLauncher> make_hvp(int64_t dtype, int64_t loss, const Tensor& segs, const Tensor& tasks,
+                                       const Tensor& slab, const Tensor& part_task_begin, int64_t d_x, int64_t ld_x) {
+  need(dtype == 0 || dtype == 1 || dtype == 3, "newton-cg: fp64, fp32 or fp32x64 (fp32 storage, fp64 accumulators)");
+  need(loss >= 0 && loss <= 2, "newton-cg: logistic, least squares or squared hinge");
+  return make_blocked(8, "newton-cg", "blocks", dtype, loss, 2, segs, tasks, slab, part_task_begin, d_x, ld_x);
+}
+
 // Sparse plan (ops/grad.py SparseGradPlan): every distinct local partition once; the plan's device
 // encoding (set_encode) forms the messages.  Tensors are kept alive by the launcher.
 std::shared_ptr<GradLauncher> make_sparse(int64_t loss, const Tensor& y, const Tensor& u, std::optional<Tensor> ell_idx,
@@ -362,6 +371,8 @@ void bind_grad_launcher(py::module& m) {
       .def_static("folds", &make_folds, py::arg("dtype"), py::arg("loss"), py::arg("folds"), py::arg("segs"),
                   py::arg("tasks"), py::arg("slab"), py::arg("part_task_begin"), py::arg("d_x"), py::arg("ld_x"))
       .def_static("precond", &make_precond, py::arg("dtype"), py::arg("loss"), py::arg("segs"), py::arg("tasks"),
+                  py::arg("slab"), py::arg("part_task_begin"), py::arg("d_x"), py::arg("ld_x"))
+      .def_static("hvp", &make_hvp, py::arg("dtype"), py::arg("loss"), py::arg("segs"), py::arg("tasks"),
                   py::arg("slab"), py::arg("part_task_begin"), py::arg("d_x"), py::arg("ld_x"))
       .def_static("sparse", &make_sparse, py::arg("loss"), py::arg("y"), py::arg("u"), py::arg("ell_idx"), py::arg("lo"),
                   py::arg("row_ptr"), py::arg("col_idx"), py::arg("vals"), py::arg("crow"), py::arg("cvals"),

@@ -16,7 +16,8 @@ namespace eh {
 
 struct GradLauncher {
   // 0 dense fused, 1 dense two-pass, 2 sparse, 3 multi-class softmax, 4 several scalar-loss models, 5 one-vs-rest,
-  // 6 K-fold cross-validation, 7 gradient + Hessian diagonal of one model (--precondition diag)
+  // 6 K-fold cross-validation, 7 gradient + Hessian diagonal of one model (--precondition diag), 8 gradient +
+  // Hessian-vector product of one model (--newton-cg J; grad_hvp.hip: blocks = 2, the model is [beta ; v])
   int kind = 0;
   int dtype = 0, loss = 0, cpl = 0, ntasks = 0, nslots = 0, ld = 0;
   KernelChoice choice{};
@@ -118,6 +119,8 @@ struct GradLauncher {
                                  gate);
       case 7:
         return grad_curv_launch(dtype, loss, segs, tasks, ntasks, stb, nparts, beta, slab, G, d_x, ld_x, st, gate);
+      case 8:
+        return grad_hvp_launch(dtype, loss, segs, tasks, ntasks, stb, nparts, beta, slab, G, d_x, ld_x, st, gate);
       default:
         return hipErrorInvalidValue;
     }

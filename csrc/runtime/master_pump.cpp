@@ -335,6 +335,43 @@ class MasterPump {
     return {lb_state_, lb_ring_};
   }
 
+  // Newton-CG run (kernels/grad_hvp.hip, newton_cg.hip; --newton-cg J): the model is [2][ld_x] (d_x data columns),
+  // block 0 beta and block 1 the CG direction; round i advances the truncated-Newton state machine with
+  // (eta, gs, l2c)[i] and the constants J, xi, tau (launchers.h NewtonCoefs).  The pump owns the state the method keeps
+  // between rounds (newton_state()), zeroed here; the kernel advances it on the device, so a captured graph of the
+  // rounds replays unchanged.  From then on combine() launches newton_cg_update, and the rounds take neither fused
+  // update path, like an L-BFGS run.  Call after set_state.
+  void set_newton_schedule(int ld_x, int d_x, int J, double xi, double tau, const std::vector<double>& eta,
+                           const std::vector<double>& gs, const std::vector<double>& l2c) {
+    arb_ready_ = false;
+    need(J >= 1 && J <= eh::kNewtonMaxInner, "newton schedule: J must be in 1..32");
+    need(xi > 0.0 && std::isfinite(xi), "newton schedule: the tolerance must be finite and > 0");
+    need(tau > 0.0 && std::isfinite(tau), "newton schedule: the step must be finite and > 0");
+    need(ld_x >= 1 && d_x >= 1 && d_x <= ld_x && 2 * static_cast<int64_t>(ld_x) == ld_ && d_ == ld_,
+         "newton schedule: 2 * ld_x must be the model length");
+    need(!blocks_ && prox_.empty() && pc_damp_.empty() && !lb_memory_ && update_rule_ == 0,
+         "newton schedule: one GD model, not with a block, prox, precond or lbfgs schedule");
+    need(beta_.defined(), "newton schedule: set_state first");
+    const size_t n = static_cast<size_t>(R_);
+    need(n > 0 && eta.size() >= n && gs.size() >= n && l2c.size() >= n, "newton schedule arrays must cover R rounds");
+    nt_J_ = J;
+    nt_ldx_ = ld_x;
+    nt_dx_ = d_x;
+    nt_xi_ = xi;
+    nt_tau_ = tau;
+    nt_eta_ = eta;
+    nt_gs_ = gs;
+    nt_l2c_ = l2c;
+    nt_state_ = at::zeros({5, ld_x}, beta_.options());
+    nt_scal_ = at::zeros({2}, beta_.options());
+    nt_phase_ = at::zeros({4}, beta_.options().dtype(at::kInt));
+  }
+  // (state fp64 [5, ld_x], scal fp64 [2], phase int32 [4]): what a checkpoint stores and a resume copies into
+  std::tuple<Tensor, Tensor, Tensor> newton_state() const {
+    need(nt_J_ > 0, "no newton schedule");
+    return {nt_state_, nt_scal_, nt_phase_};
+  }
+
   // --delay-on worker: virtual delays the collector applies to REMOTE messages (the worker ranks
   // are physically late themselves); default: the same table as the local messages.
   void set_remote_delays(const std::vector<double>& delays) {
@@ -607,7 +644,7 @@ class MasterPump {
         if (!graph) decode_round(i);
         char* g = ring_slot(G_, g_rows_, i);
         eh::LocalUpdate up;
-        if (fused_update_ && prox_.empty() && pc_damp_.empty() && !lb_memory_ && launcher_->can_fuse_update() &&
+        if (fused_update_ && prox_.empty() && pc_damp_.empty() && !lb_memory_ && !nt_J_ && launcher_->can_fuse_update() &&
             local_update(i, useds[i - a], g, st + i + 1, &up)) {
           hcheck(launcher_->launch_update(beta_row(i), g, up, stream_), "local gradient + update");
           continue;
@@ -666,6 +703,7 @@ class MasterPump {
     if (!prox_.empty()) return "proximal step after the update (L1 penalty)";
     if (!pc_damp_.empty()) return "preconditioned step (the update divides by the decoded curvature diagonal)";
     if (lb_memory_) return "L-BFGS step (the update keeps a ring of pairs and runs as one workgroup)";
+    if (nt_J_) return "Newton-CG step (the update runs the CG recurrences as one workgroup)";
     if (blocks_) return "per-model update coefficients (multi-model run)";
     if (comm_) return "messages travel over " + comm_->kind() + " (the arbiter polls IPC counters)";
     if (remote_.empty() || arb_src_.empty()) return "no remote workers";
@@ -908,7 +946,14 @@ class MasterPump {
       else
         eh::set_block_coefs(bc, 1, ld_, d_, &decay_[i], &gm_[i], &l2_[i]);
     };
-    if (lb_memory_) {  // the quasi-Newton step
+    if (nt_J_) {  // one round of truncated Newton
+      const eh::NewtonCoefs nc{nt_ldx_, nt_dx_, nt_eta_[i], nt_gs_[i], nt_l2c_[i], nt_xi_, nt_tau_, nt_J_};
+      hcheck(eh::newton_cg_update_launch(a, acc_, acc_, beta_.data_ptr<double>(),
+                                         hist_.data_ptr<double>() + static_cast<int64_t>(i) * ld_, beta_row(i + 1),
+                                         nt_state_.data_ptr<double>(), nt_scal_.data_ptr<double>(),
+                                         nt_phase_.data_ptr<int>(), nc, stream_, stamp),
+             "newton_cg_update");
+    } else if (lb_memory_) {  // the quasi-Newton step
       const eh::LbfgsCoefs lc{ld_, d_, lb_eta_[i], lb_gs_[i], lb_l2c_[i], lb_tau_, lb_memory_};
       hcheck(eh::lbfgs_update_launch(a, acc_, acc_, beta_.data_ptr<double>(),
                                      hist_.data_ptr<double>() + static_cast<int64_t>(i) * ld_, beta_row(i + 1),
@@ -1230,6 +1275,11 @@ class MasterPump {
   double lb_tau_ = 1.0;
   std::vector<double> lb_eta_, lb_gs_, lb_l2c_;
   Tensor lb_state_, lb_ring_;
+  // set_newton_schedule: [R] each; nt_J_ 0 = no Newton-CG
+  int nt_J_ = 0, nt_ldx_ = 0, nt_dx_ = 0;
+  double nt_xi_ = 0.1, nt_tau_ = 1.0;
+  std::vector<double> nt_eta_, nt_gs_, nt_l2c_;
+  Tensor nt_state_, nt_scal_, nt_phase_;
   std::vector<double> prox_;  // set_prox_schedule: soft thresholds [R * max(1, blocks_)]; empty = no proximal step
   int repeat_ = 1;
   int update_rule_ = 0, stop_rule_ = 0, k_ = 0;
@@ -1291,6 +1341,8 @@ void bind_master_pump(py::module& m) {
       .def("set_precond_schedule", &MasterPump::set_precond_schedule)
       .def("set_lbfgs_schedule", &MasterPump::set_lbfgs_schedule)
       .def("lbfgs_state", &MasterPump::lbfgs_state)
+      .def("set_newton_schedule", &MasterPump::set_newton_schedule)
+      .def("newton_state", &MasterPump::newton_state)
       .def("set_decode", &MasterPump::set_decode)
       .def("add_table", &MasterPump::add_table)
       .def("begin", &MasterPump::begin, py::call_guard<py::gil_scoped_release>())

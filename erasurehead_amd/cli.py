@@ -54,6 +54,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "--lr and its schedule give the GD step taken while no pair is held")
     g.add_argument("--lbfgs-step", type=float, default=None, metavar="TAU",
                    help="--lbfgs: beta -= TAU * p (default 1)")
+    g.add_argument("--newton-cg", type=int, default=0, metavar="J",
+                   help="truncated Newton (Newton-CG) steps of the master with at most J in 1..32 CG steps per outer "
+                        "iteration (0 = off): every message carries a Hessian-vector product next to the gradient; an "
+                        "outer iteration costs 1 + (CG steps used) rounds; --lr and its schedule give the GD step taken "
+                        "where CG meets no positive curvature")
+    g.add_argument("--newton-tol", type=float, default=None, metavar="XI",
+                   help="--newton-cg: the inner loop ends when |CG residual| <= XI * |gradient| (default 0.1)")
+    g.add_argument("--newton-step", type=float, default=None, metavar="TAU",
+                   help="--newton-cg: beta += TAU * x (default 1)")
     g.add_argument("--num-itrs", type=int, default=100)
     g.add_argument("--lr", type=float, default=10.0)
     g.add_argument("--lr-schedule", default="const", choices=["const", "invscaling", "exponential"],
@@ -157,6 +166,9 @@ def parse(argv: List[str]):
      num_collect, add_delay, update_rule) = a.positional
     if a.lbfgs_step is not None and not a.lbfgs:
         raise ValueError("--lbfgs-step: needs --lbfgs M")
+    for flag, v in (("--newton-tol", a.newton_tol), ("--newton-step", a.newton_step)):
+        if v is not None and not a.newton_cg:
+            raise ValueError(f"{flag}: needs --newton-cg J")
     cfg = RunConfig(int(n_procs), int(n_rows), int(n_cols), input_dir, int(is_real), dataset, int(is_coded),
                     int(n_stragglers), int(partitions), int(coded_ver), int(num_collect), int(add_delay),
                     update_rule, num_itrs=a.num_itrs, alpha=a.alpha, lr=a.lr,
@@ -174,7 +186,9 @@ def parse(argv: List[str]):
                     sweep_alpha=a.alphas, sweep_lr=a.lrs, l1=a.l1, sweep_l1=a.l1s,
                     class_weight=a.class_weight, sample_weights=a.sample_weights, ovr=a.ovr, cv=a.cv,
                     precondition=a.precondition, precondition_damping=a.precondition_damping,
-                    lbfgs=a.lbfgs, lbfgs_step=1.0 if a.lbfgs_step is None else a.lbfgs_step)
+                    lbfgs=a.lbfgs, lbfgs_step=1.0 if a.lbfgs_step is None else a.lbfgs_step,
+                    newton_cg=a.newton_cg, newton_tol=0.1 if a.newton_tol is None else a.newton_tol,
+                    newton_step=1.0 if a.newton_step is None else a.newton_step)
     return cfg, a
 
 

@@ -80,6 +80,12 @@ class RunConfig:
     # beta -= lbfgs_step * p with p the two-loop direction; the run's GD step (lr, its schedule) while no pair is held
     lbfgs: int = 0
     lbfgs_step: float = 1.0
+    # Truncated Newton (Newton-CG) steps of the master (csrc/kernels/grad_hvp.hip, newton_cg.hip): newton_cg = J in
+    # 1..32, the most CG steps per outer iteration (0 = off); an outer iteration costs 1 + (CG steps used) rounds and
+    # ends when the CG residual falls to newton_tol times the gradient norm; beta += newton_step * x
+    newton_cg: int = 0
+    newton_tol: float = 0.1
+    newton_step: float = 1.0
     # (alpha, lr) sweep: M = 2..8 models trained in one run from one pass over X per round (ops/multimodel.py).
     # The lists are zipped; an absent list or one of length 1 is broadcast (absent: the run's alpha / lr).
     sweep_alpha: Optional[List[float]] = None
@@ -172,6 +178,7 @@ class RunConfig:
             self._check_cv()
         self._check_precondition()
         self._check_lbfgs()
+        self._check_newton()
         if self.loss == "softmax":
             self.classes = 2 if self.classes is None else int(self.classes)
             if not 2 <= self.classes <= 8:
@@ -286,6 +293,43 @@ class RunConfig:
             raise ValueError("--lbfgs: cannot be combined with --l1 (OWL-QN is not implemented)")
         if self.precondition != "none":
             raise ValueError("--lbfgs: cannot be combined with --precondition diag")
+
+    def _check_newton(self) -> None:
+        """The limits of a Newton-CG run that the configuration alone decides, each a ValueError naming the flag."""
+        if isinstance(self.newton_cg, bool) or self.newton_cg != int(self.newton_cg):
+            raise ValueError(f"--newton-cg: J must be an integer in 1..32 (0 = off), got {self.newton_cg!r}")
+        self.newton_cg, self.newton_tol, self.newton_step = int(self.newton_cg), float(self.newton_tol), \
+            float(self.newton_step)
+        if not 0 <= self.newton_cg <= 32:
+            raise ValueError(f"--newton-cg: J must be in 1..32 (0 = off), got {self.newton_cg}")
+        if not (np.isfinite(self.newton_tol) and self.newton_tol > 0):
+            raise ValueError(f"--newton-tol: must be finite and > 0, got {self.newton_tol}")
+        if not (np.isfinite(self.newton_step) and self.newton_step > 0):
+            raise ValueError(f"--newton-step: must be finite and > 0, got {self.newton_step}")
+        if self.newton_cg == 0:
+            if self.newton_tol != 0.1:  # (the command line also refuses an explicit default: cli.parse)
+                raise ValueError("--newton-tol: needs --newton-cg J")
+            if self.newton_step != 1.0:
+                raise ValueError("--newton-step: needs --newton-cg J")
+            return
+        if self.update_rule == "AGD":
+            raise ValueError("--newton-cg: the update rule must be GD (no momentum on a Newton step)")
+        if self.loss == "softmax":
+            raise ValueError("--newton-cg: not supported with --loss softmax (one model of a scalar loss)")
+        if self.ovr is not None:
+            raise ValueError("--newton-cg: cannot be combined with --ovr")
+        if self.cv is not None:
+            raise ValueError("--newton-cg: cannot be combined with --cv")
+        if self.sweep_alpha is not None or self.sweep_lr is not None or self.sweep_l1 is not None:
+            raise ValueError("--newton-cg: cannot be combined with a sweep (--alphas / --lrs / --l1s)")
+        if float(self.l1) != 0:
+            raise ValueError("--newton-cg: cannot be combined with --l1 (a proximal Newton step is not implemented)")
+        if self.precondition != "none":
+            raise ValueError("--newton-cg: cannot be combined with --precondition diag")
+        if self.lbfgs:
+            raise ValueError("--newton-cg: cannot be combined with --lbfgs")
+        if self.class_weight is not None or self.sample_weights is not None:
+            raise ValueError("--newton-cg: --class-weight / --sample-weights are not supported")
 
     def _sweep_lists(self) -> Optional[Tuple[List[float], List[float], List[float]]]:
         """([alpha_k], [lr_k], [l1_k]) of a sweep run, every list broadcast to the M models; None without a list."""

@@ -1,8 +1,10 @@
 """What kind of model a run trains, decided once (ModelSpec), and its update schedule (UpdateSchedule).
 
-Six kinds share the engine: a ``single`` model of a scalar loss, ``softmax`` and one-vs-rest (``ovr``) with one
+Seven kinds share the engine: a ``single`` model of a scalar loss, ``softmax`` and one-vs-rest (``ovr``) with one
 block per class, a ``sweep`` of M (alpha, lr, l1) models of one scalar loss, the K fold models of a K-fold
-cross-validation (``cv``) of one scalar loss, and a single model stepped by a Jacobi preconditioner (``precond``,
+cross-validation (``cv``) of one scalar loss, a single model stepped by truncated Newton (``newton``, --newton-cg J:
+block 0 is the model, block 1 the CG direction on the wire, the Hessian-vector product in every message and exact zeros
+in every stored iterate), and a single model stepped by a Jacobi preconditioner (``precond``,
 --precondition diag: block 0 is the model, block 1 the place of the curvature diagonal in every message and exact
 zeros in the model).  Everything the engine keeps
 (beta, messages, history, checkpoints) is one vector of ``ld`` elements, block-major ``[blocks][ld_x]`` with
@@ -24,13 +26,14 @@ from ..models.losses import (LEAST_SQUARES, LOGISTIC, LOSS_CHOICES, SOFTMAX, SQU
                              check_classes, is_classification, weighted_kind)
 from ..ops.cv import CvGradPlan
 from ..ops.grad import DenseGradPlan, SharedGradPlan, SparseGradPlan
+from ..ops.hvp import HvpGradPlan
 from ..ops.multimodel import MultiModelGradPlan
 from ..ops.ovr import OvrGradPlan
 from ..ops.precision import Precision
 from ..ops.precond import PrecondGradPlan
 from ..ops.softmax import SoftmaxGradPlan
 from ..ops.update import (combine_update, combine_update_blocks, combine_update_precond, combine_update_prox,
-                          lbfgs_state, lbfgs_update)
+                          lbfgs_state, lbfgs_update, newton_cg_update, newton_state)
 
 SQHINGE_PREFIX = "sqhinge_"  # result files of squared-hinge runs (next to the logistic names)
 SOFTMAX_PREFIX = "softmax_"
@@ -38,6 +41,7 @@ OVR_PREFIX = "ovr_"  # result files of one-vs-rest runs (before sqhinge_)
 WEIGHTED_PREFIX = "weighted_"  # result files of runs with class / sample weights
 PRECOND_PREFIX = "precond_"  # result files of --precondition diag runs (before sqhinge_)
 LBFGS_PREFIX = "lbfgs_"  # result files of --lbfgs runs (before sqhinge_)
+NEWTON_PREFIX = "newton_"  # result files of --newton-cg runs (before sqhinge_)
 
 
 def sweep_prefix(k: int) -> str:
@@ -50,7 +54,7 @@ def cv_prefix(k: int) -> str:
 
 @dataclass(frozen=True)
 class ModelSpec:
-    kind: str  # "single" | "softmax" | "ovr" | "sweep" | "cv" | "precond"
+    kind: str  # "single" | "softmax" | "ovr" | "sweep" | "cv" | "precond" | "newton"
     loss: int  # models/losses.py code, the weighted code of a weighted run; one-vs-rest: the binary loss
     weighted: bool  # class / sample weights: the labels carry them (data/source.py WeightedSource)
     classes: int  # softmax, one-vs-rest: the class blocks; 1 otherwise
@@ -74,6 +78,11 @@ class ModelSpec:
     # --lbfgs M: the pairs kept (0 = off) and the step tau of beta -= tau p; the model's layout is the single model's
     lbfgs: int = 0
     lbfgs_step: float = 1.0
+    # --newton-cg J: the most CG steps per outer iteration (0 = off), the relative tolerance xi of the inner loop and
+    # the step tau of beta += tau x
+    newton_cg: int = 0
+    newton_tol: float = 0.1
+    newton_step: float = 1.0
 
     # ---------------------------------------------------------------- resolution and rejections
     @classmethod
@@ -137,6 +146,16 @@ class ModelSpec:
             if getattr(scheme, "fixed_agd", False):
                 raise ValueError("--lbfgs: this scheme always updates by AGD; the update rule must be GD")
             extra = dict(lbfgs=int(cfg.lbfgs), lbfgs_step=float(cfg.lbfgs_step))
+        if cfg.newton_cg:  # (the config rejected what it can see; these need the resolved run)
+            if kind != "single":
+                raise ValueError(f"--newton-cg: not supported with a {kind} model (one model of a scalar loss)")
+            if weighted:  # a source that brings sample weights of its own
+                raise ValueError("--newton-cg: class / sample weights are not supported")
+            if getattr(scheme, "fixed_agd", False):
+                raise ValueError("--newton-cg: this scheme always updates by AGD; the update rule must be GD")
+            kind = "newton"
+            extra = dict(newton_cg=int(cfg.newton_cg), newton_tol=float(cfg.newton_tol),
+                         newton_step=float(cfg.newton_step))
         d_x = int(cfg.n_cols)
         spec = cls(kind, loss, weighted, classes, models, d_x, prec.ld(d_x), float(cfg.l1),
                    [a for a, _ in sweep] if sweep else None, [x for _, x in sweep] if sweep else None,
@@ -151,6 +170,8 @@ class ModelSpec:
             CvGradPlan.check_supported(prec, loss, spec.models, sparse, spec.ld_x, gpu)
         elif kind == "precond":
             PrecondGradPlan.check_supported(prec, loss, sparse, spec.ld_x, gpu)
+        elif kind == "newton":
+            HvpGradPlan.check_supported(prec, loss, sparse, spec.ld_x, gpu)
         return spec
 
     def check_partitions(self, parts, rows_per_partition: int) -> None:
@@ -171,8 +192,9 @@ class ModelSpec:
 
     @property
     def blocks(self) -> int:
-        """The blocks of the vector: a preconditioned run's model is followed by the curvature diagonal's block."""
-        return 2 if self.kind == "precond" else self.model_blocks
+        """The blocks of the vector: a preconditioned run's model is followed by the curvature diagonal's block, a
+        Newton-CG run's by the CG direction's."""
+        return 2 if self.kind in ("precond", "newton") else self.model_blocks
 
     @property
     def ld(self) -> int:
@@ -240,7 +262,7 @@ class ModelSpec:
         B = np.asarray(betaset, dtype=np.float64)
         full = np.zeros((B.shape[0], self.ld))
         full[:, : self.d] = B
-        if self.kind == "precond":  # scored as the single model in block 0
+        if self.kind in ("precond", "newton"):  # scored as the single model in block 0
             return np.ascontiguousarray(full[:, : self.ld_x])
         return full.reshape(B.shape[0] * self.blocks, self.ld_x)
 
@@ -282,6 +304,8 @@ class ModelSpec:
             return CvGradPlan(messages, parts, self.prec, self.loss, self.models, self.d_x)
         if self.kind == "precond":
             return PrecondGradPlan(messages, parts, self.prec, self.loss, self.d_x)
+        if self.kind == "newton":
+            return HvpGradPlan(messages, parts, self.prec, self.loss, self.d_x)
 
         def one(msgs):
             if self.sparse:
@@ -330,10 +354,10 @@ class ModelSpec:
 
     def result_names(self, names: Dict[str, str], model_prefix: str = "") -> Dict[str, str]:
         """The scheme's result names under the run's prefixes: ``sweep{k}_`` / ``cv{k}_`` first, then ``softmax_`` /
-        ``ovr_``, ``weighted_``, ``precond_``, ``lbfgs_``, ``sqhinge_``."""
+        ``ovr_``, ``weighted_``, ``precond_``, ``lbfgs_``, ``newton_``, ``sqhinge_``."""
         p = model_prefix + {"softmax": SOFTMAX_PREFIX, "ovr": OVR_PREFIX}.get(self.kind, "")
         p += (WEIGHTED_PREFIX if self.weighted else "") + (PRECOND_PREFIX if self.kind == "precond" else "")
-        p += LBFGS_PREFIX if self.lbfgs else ""
+        p += (LBFGS_PREFIX if self.lbfgs else "") + (NEWTON_PREFIX if self.kind == "newton" else "")
         p += (SQHINGE_PREFIX if base_kind(self.loss) == SQUARED_HINGE else "")
         return {k: p + v for k, v in names.items()}
 
@@ -351,6 +375,8 @@ class ModelSpec:
             rep.update(precondition=self.precondition, damping=self.damping)
         if self.lbfgs:
             rep.update(lbfgs=self.lbfgs, lbfgs_step=self.lbfgs_step)
+        if self.kind == "newton":
+            rep.update(newton_cg=self.newton_cg, newton_tol=self.newton_tol, newton_step=self.newton_step)
         rep.update(l1=list(self.sweep_l1) if self.kind == "sweep" else self.l1, prox=bool(self.prox),
                    weighted=bool(self.weighted))
         return rep
@@ -375,6 +401,10 @@ class ModelSpec:
         if self.lbfgs:  # (the trainer adds the state itself: lbfgs_state, lbfgs_ring)
             state["lbfgs"] = int(self.lbfgs)
             state["lbfgs_step"] = float(self.lbfgs_step)
+        if self.kind == "newton":  # (the trainer adds the state itself: newton_state, newton_scal, newton_phase)
+            state["newton_cg"] = int(self.newton_cg)
+            state["newton_tol"] = float(self.newton_tol)
+            state["newton_step"] = float(self.newton_step)
         return state
 
     def check_checkpoint(self, st, path: str, weight_spec) -> None:
@@ -416,6 +446,15 @@ class ModelSpec:
         if self.lbfgs and (st.get("lbfgs_state") is None or st.get("lbfgs_ring") is None or
                            tuple(st["lbfgs_state"].shape) != (2 * self.lbfgs + 3, self.ld)):
             raise ValueError(f"checkpoint {path} lacks the L-BFGS state of a --lbfgs {self.lbfgs} run")
+        have_nt = (int(st.get("newton_cg", 0)), float(st.get("newton_tol", 0.1)), float(st.get("newton_step", 1.0)))
+        if have_nt != (self.newton_cg, float(self.newton_tol), float(self.newton_step)):
+            raise ValueError(f"checkpoint {path} was written by a run with newton_cg = {have_nt[0]}, newton_tol = "
+                             f"{have_nt[1]:g}, newton_step = {have_nt[2]:g}; this run has newton_cg = {self.newton_cg}, "
+                             f"newton_tol = {self.newton_tol:g}, newton_step = {self.newton_step:g} "
+                             f"(--newton-cg / --newton-tol / --newton-step)")
+        if self.newton_cg and (any(st.get(k) is None for k in ("newton_state", "newton_scal", "newton_phase")) or
+                               tuple(st["newton_state"].shape) != (5, self.ld_x)):
+            raise ValueError(f"checkpoint {path} lacks the Newton-CG state of a --newton-cg {self.newton_cg} run")
         have_w = st.get("weights")
         if have_w != weight_spec:
             raise ValueError(f"checkpoint {path} was written by a run with weights = {have_w}; this run has "
@@ -448,6 +487,11 @@ class UpdateSchedule:
     lbfgs: Optional[np.ndarray] = None
     lbfgs_cfg: Tuple[int, float] = (0, 1.0)
     lbfgs_state: Optional[tuple] = None
+    # --newton-cg J: [3, R] eta, gs, l2c (UpdateRule.newton_coeffs), (ld_x, d_x, J, xi, tau), and for the Python round
+    # loop the (state, scal, phase) tensors of ops/update.py newton_state that the rounds advance; None without
+    newton: Optional[np.ndarray] = None
+    newton_cfg: Tuple[int, int, int, float, float] = (0, 0, 0, 0.1, 1.0)
+    newton_state: Optional[tuple] = None
 
     @classmethod
     def build(cls, rule: UpdateRule, rounds: int, eta, sweep_etas, spec: ModelSpec) -> "UpdateSchedule":
@@ -483,13 +527,23 @@ class UpdateSchedule:
         lb = None
         if spec.lbfgs:
             lb = np.array([rule.lbfgs_coeffs(i, float(eta[i])) for i in range(R)], dtype=np.float64).reshape(R, 3).T
-        return cls(decay, gm, l2, thr, theta, code, *block, single, precond, pblock, lb, (spec.lbfgs, spec.lbfgs_step))
+        nt = None
+        if spec.kind == "newton":
+            nt = np.array([rule.newton_coeffs(i, float(eta[i])) for i in range(R)], dtype=np.float64).reshape(R, 3).T
+        return cls(decay, gm, l2, thr, theta, code, *block, single, precond, pblock, lb, (spec.lbfgs, spec.lbfgs_step),
+                   None, nt, (spec.ld_x, spec.d_x, spec.newton_cg, spec.newton_tol, spec.newton_step))
 
     def apply(self, i: int, msgs, coefs, beta, u, hist, beta_w) -> None:
         """Round i's combine + update (ops/update.py): with a threshold the proximal form (a single model as one
         block), a sweep without one the blocked form, anything else the plain one."""
         theta = float(self.theta[i])
-        if self.lbfgs is not None:
+        if self.newton is not None:
+            if self.newton_state is None:
+                self.newton_state = newton_state(self.newton_cfg[0], beta.device)
+            ld_x, d_x, J, xi, tau = self.newton_cfg
+            newton_cg_update(msgs, coefs, beta, *self.newton_state, ld_x, d_x, J, *(float(x) for x in self.newton[:, i]),
+                             xi, tau, hist=hist, beta_w=beta_w)
+        elif self.lbfgs is not None:
             if self.lbfgs_state is None:
                 self.lbfgs_state = lbfgs_state(self.lbfgs_cfg[0], beta.numel(), beta.device)
             lbfgs_update(msgs, coefs, beta, *self.lbfgs_state, self.block_d, *(float(x) for x in self.lbfgs[:, i]),
@@ -522,3 +576,5 @@ class UpdateSchedule:
             pump.set_precond_schedule(*self.precond_block, *(x.tolist() for x in self.precond))
         if self.lbfgs is not None:  # the pump owns the state (pump.lbfgs_state()); off both fused update paths too
             pump.set_lbfgs_schedule(self.lbfgs_cfg[0], self.lbfgs_cfg[1], *(x.tolist() for x in self.lbfgs))
+        if self.newton is not None:  # the pump owns the state (pump.newton_state()); off both fused update paths too
+            pump.set_newton_schedule(*self.newton_cfg, *(x.tolist() for x in self.newton))

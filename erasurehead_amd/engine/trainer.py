@@ -56,7 +56,7 @@ from ..models.losses import UpdateRule
 from ..ops.blockplan import BlockGradPlan
 from ..ops.grad import SharedGradPlan, SparseGradPlan
 from ..ops.precision import get_precision
-from ..ops.update import lbfgs_state
+from ..ops.update import lbfgs_state, newton_state
 from ..parallel.collector import ArrivalCollector
 from ..parallel.dist import DistEnv
 from ..parallel.placement import make_shards, place_spread, place_units
@@ -115,6 +115,7 @@ def _mean_us(ms, a0: int = 0) -> Optional[float]:
 
 class Trainer:
     lbfgs_state = None  # the master of a --lbfgs run: (state, ring) of ops/update.py lbfgs_state
+    newton_state = None  # the master of a --newton-cg run: (state, scal, phase) of ops/update.py newton_state
 
     def __init__(self, cfg: RunConfig, env: Optional[DistEnv] = None, source: Optional[DataSource] = None,
                  scheme: Optional[Scheme] = None):
@@ -358,6 +359,8 @@ class Trainer:
             self.u = torch.zeros(ld, dtype=torch.float64, device=dev)
             # --lbfgs: the ring of pairs and the previous round's beta / gradient (ops/update.py lbfgs_state)
             self.lbfgs_state = lbfgs_state(self.model.lbfgs, ld, dev) if self.model.lbfgs else None
+            # --newton-cg: the CG vectors, scalars and counters (ops/update.py newton_state)
+            self.newton_state = newton_state(self.model.ld_x, dev) if self.model.newton_cg else None
             self.hist = torch.zeros((R, ld), dtype=torch.float64, device=dev)
             self.beta_in = torch.zeros((R + 1, ld), dtype=acc, device=dev)
             self.loc_index = {(m.worker, m.part, m.shard): j for j, m in enumerate(self.local_msgs)}
@@ -434,6 +437,8 @@ class Trainer:
         self.beta.copy_(torch.from_numpy(packed).to(self.beta.device))
         self.u.zero_()
         for t in self.lbfgs_state or ():  # a second run() starts without pairs; a resume overwrites it, as it does u
+            t.zero_()
+        for t in self.newton_state or ():  # ... and with a gradient round
             t.zero_()
         self.beta_in[0].copy_(self.beta.to(self.beta_in.dtype))
         self.beta0 = packed[: self.d]
@@ -778,6 +783,7 @@ class Trainer:
         cfg = self.cfg
         sched = UpdateSchedule.build(self.update, cfg.num_itrs, cfg.eta(), cfg.sweep_etas(), self.model)
         sched.lbfgs_state = self.lbfgs_state  # the Python loop's rounds advance the trainer's own state
+        sched.newton_state = self.newton_state
         return sched
 
     def _result(self, timeset, worker_timeset, loop_time, total, timeouts, arrivals_log, timed_start, t_timed0,
@@ -889,6 +895,11 @@ class Trainer:
             for dst, src in zip(owned, self.lbfgs_state):
                 dst.copy_(src)
             self.lbfgs_state = tuple(owned)
+        if self.newton_state is not None:
+            owned = pump.newton_state()
+            for dst, src in zip(owned, self.newton_state):
+                dst.copy_(src)
+            self.newton_state = tuple(owned)
         if self.physical:  # remote messages are really late: the collector applies no virtual delay to them
             pump.set_remote_delays([float(x) for x in self._remote_delays(delay_table).ravel()])
         if self._clocks and tx is not None and (self.physical or cfg.device_records):
@@ -1270,6 +1281,12 @@ class Trainer:
         if self.lbfgs_state is not None:
             self.lbfgs_state[0].copy_(st["lbfgs_state"].to(dev))
             self.lbfgs_state[1].copy_(st["lbfgs_ring"].to(dev))
+        if self.newton_state is not None:  # mid-iteration, the wire model's block 1 is the state's direction
+            for dst, key in zip(self.newton_state, ("newton_state", "newton_scal", "newton_phase")):
+                dst.copy_(st[key].to(dev))
+            if int(self.newton_state[2][0]) == 1:
+                x = self.model.ld_x
+                self.beta_in[nxt, x:].copy_(self.newton_state[0][2].to(self.beta_in.dtype))
         self._restored = {"timeset": st["timeset"].numpy(), "worker_timeset": st["worker_timeset"].numpy()}
         return nxt
 
@@ -1287,6 +1304,8 @@ class Trainer:
         state.update(self.model.checkpoint_state(self.weight_spec))
         if self.lbfgs_state is not None:
             state["lbfgs_state"], state["lbfgs_ring"] = (t.cpu() for t in self.lbfgs_state)
+        if self.newton_state is not None:
+            state["newton_state"], state["newton_scal"], state["newton_phase"] = (t.cpu() for t in self.newton_state)
         if getattr(self.scheme, "B", None) is not None:
             state["B"] = torch.from_numpy(np.ascontiguousarray(self.scheme.B, dtype=np.float64))
         tmp = path + ".tmp"

@@ -298,6 +298,20 @@ def precond_unpack(betaset: np.ndarray, d_x: Optional[int] = None) -> np.ndarray
     return b[:, : (b.shape[1] // 2 if d_x is None else int(d_x))]
 
 
+def hvp_grad(kind: int, X, y: np.ndarray, beta: np.ndarray, v: np.ndarray, coef=None) -> np.ndarray:
+    """[2, d]: row 0 the scalar-loss gradient sum r_i x_i at beta, row 1 its Hessian applied to v,
+    sum l''(z_i) (x_i . v) x_i (what one partition contributes to a --newton-cg message, times coef)."""
+    X = np.asarray(X, dtype=np.float64)
+    u = X.T.dot(curvature(kind, X.dot(beta), y) * X.dot(v))
+    return np.stack([_GRADS[kind](X, y, beta, coef), u if coef is None else coef * u])
+
+
+def newton_unpack(betaset: np.ndarray, d_x: Optional[int] = None) -> np.ndarray:
+    """[R, 2 * ld_x] trajectory of a --newton-cg run (as the engine stores it) -> block 0 [R, d_x], the model (d_x
+    absent: all ld_x columns); block 1 is the CG direction's place on the wire and is zero in every stored row."""
+    return precond_unpack(betaset, d_x)
+
+
 def worker_grad(kind: int, X, y, beta, coef=None) -> np.ndarray:
     if kind == SOFTMAX:  # beta: the flattened [C, X.shape[1]] model; returns the gradient flattened alike
         d = X.shape[1]
@@ -387,6 +401,30 @@ class LbfgsState:
     pairs: list = dataclasses.field(default_factory=list)
     beta_prev: Optional[np.ndarray] = None
     g_prev: Optional[np.ndarray] = None
+
+
+@dataclass
+class NewtonState:
+    """What the oracle UpdateRule.step_newton remembers between rounds (the engines keep ops/update.py newton_state):
+    the accumulated step x, the CG residual r, the direction (what the next round's workers apply the Hessian to; zeros
+    before a gradient round), the gradient g0 at the outer iterate, rs = r . r, g0norm2 = g0 . g0, and the counters
+    phase (0: a gradient round is next, 1: a CG round), inner (CG steps taken in this outer iteration), mode (the last
+    round's, NEWTON_MODES) and outer (outer iterations finished)."""
+
+    x: Optional[np.ndarray] = None
+    r: Optional[np.ndarray] = None
+    direction: Optional[np.ndarray] = None
+    g0: Optional[np.ndarray] = None
+    rs: float = 0.0
+    g0norm2: float = 0.0
+    phase: int = 0
+    inner: int = 0
+    mode: int = 0
+    outer: int = 0
+
+
+# the last round's mode (csrc/kernels/launchers.h NewtonMode)
+NEWTON_MODES = ("start", "continue", "step-tolerance", "step-cap", "step-curvature", "gd-curvature", "gd-gradient")
 
 
 @dataclass
@@ -483,6 +521,60 @@ class UpdateRule:
             beta -= tau * q if mode == 0 else eta * G
         state.beta_prev, state.g_prev = b, G
         return mode
+
+    def newton_coeffs(self, i: int, eta: float) -> Tuple[float, float, float]:
+        """(eta, gs, l2c) of round i's Newton-CG step: G = gs g + l2c beta and H v = gs u + l2c v, as lbfgs_coeffs'."""
+        if self.rule != "GD":
+            raise ValueError("--newton-cg: the update rule must be GD")
+        return float(eta), self.grad_scale / self.n_samples, 2.0 * self.alpha
+
+    def step_newton(self, i: int, eta: float, beta: np.ndarray, g: np.ndarray, u: np.ndarray, state: "NewtonState",
+                    J: int, xi: float, tau: float) -> int:
+        """One round of truncated Newton (Newton-CG) in place, from the decoded message sums g (block 0) and u (block
+        1: the loss Hessian applied to state.direction): the plain vector-space recurrences of linear CG on
+        H x = -G, one step per round.  beta moves only in the round that ends an outer iteration; state.direction is
+        what the next round's workers need in block 1 (zeros after such a round).  Returns the round's mode (an index
+        into NEWTON_MODES).  The oracle of csrc/kernels/newton_cg.hip and the step of the Python round loop."""
+        eta, gs, l2c = self.newton_coeffs(i, eta)
+        s = state
+        ok = lambda v: bool(np.isfinite(v) and v > 0)  # noqa: E731
+        with np.errstate(all="ignore"):
+            if s.phase != 1:
+                G = gs * g + l2c * beta
+                rs = float(G.dot(G))
+                s.g0, s.inner = G, 0
+                if ok(rs):
+                    s.x, s.r, s.direction = np.zeros_like(G), -G, -G
+                    s.rs = s.g0norm2 = rs
+                    s.mode = 0
+                else:
+                    s.mode = 6
+            else:
+                Hv = gs * u + l2c * s.direction
+                kappa = float(s.direction.dot(Hv))
+                if not ok(kappa):
+                    s.mode = 5 if s.inner == 0 else 4
+                else:
+                    a = s.rs / kappa
+                    s.x = s.x + a * s.direction
+                    s.r = s.r - a * Hv
+                    rs = float(s.r.dot(s.r))
+                    s.inner += 1
+                    if not rs > xi * xi * s.g0norm2:
+                        s.mode = 2
+                    elif s.inner >= J:
+                        s.mode = 3
+                    else:
+                        s.mode = 1
+                        s.direction = s.r + (rs / s.rs) * s.direction
+                        s.rs = rs
+            if s.mode in (0, 1):
+                s.phase = 1
+            else:
+                beta += -eta * s.g0 if s.mode >= 5 else tau * s.x
+                s.phase, s.outer = 0, s.outer + 1
+                s.direction = np.zeros_like(beta)
+        return s.mode
 
     def apply(self, i: int, eta: float, beta: np.ndarray, u: np.ndarray, g: np.ndarray) -> None:
         """In-place host update (oracle of the combine_update kernel; with l1 > 0 of combine_update_prox: the new

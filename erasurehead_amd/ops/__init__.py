@@ -6,6 +6,7 @@ from .multimodel import MultiModelGradPlan
 from .ovr import OvrGradPlan
 from .cv import CvGradPlan
 from .precond import PrecondGradPlan
+from .hvp import HvpGradPlan
 from .precision import PRECISIONS, Precision, get_precision
 from .update import (combine_update, combine_update_blocks, combine_update_precond, combine_update_prox, lbfgs_pairs,
-                     lbfgs_state, lbfgs_update)
+                     lbfgs_state, lbfgs_update, newton_cg_update, newton_state)

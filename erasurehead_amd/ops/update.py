@@ -187,6 +187,97 @@ def lbfgs_update(msgs: Sequence[torch.Tensor], coefs: Sequence[float], beta: tor
         beta_w[:d] = new.to(beta_w.dtype)
 
 
+NEWTON_MAX_INNER = 32  # csrc/kernels/launchers.h kNewtonMaxInner
+
+
+def newton_state(ld_x: int, device=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """A fresh Newton-CG state for a model of ``ld_x`` columns: ``state`` fp64 ``[5, ld_x]`` (the accumulated step x,
+    the CG residual, the direction, the gradient at the outer iterate and a scratch row that holds H dir within a
+    round), ``scal`` fp64 ``[2]`` (rs, g0norm2) and ``phase`` int32 ``[4]`` (0 / 1: a gradient / a CG round is next,
+    the CG steps taken in this outer iteration, the last round's mode -- models/losses.py NEWTON_MODES -- and the outer
+    iterations finished).  ``newton_cg_update`` advances all three in place."""
+    return (torch.zeros((5, int(ld_x)), dtype=torch.float64, device=device),
+            torch.zeros(2, dtype=torch.float64, device=device), torch.zeros(4, dtype=torch.int32, device=device))
+
+
+def newton_cg_update(msgs: Sequence[torch.Tensor], coefs: Sequence[float], beta: torch.Tensor, state: torch.Tensor,
+                     scal: torch.Tensor, phase: torch.Tensor, ld_x: int, d_x: int, J: int, eta: float, gs: float,
+                     l2c: float, xi: float, tau: float, hist: Optional[torch.Tensor] = None,
+                     beta_w: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None) -> None:
+    """One round of truncated Newton on the state of :func:`newton_state` (csrc/kernels/newton_cg.hip).  beta, the
+    messages and beta_w are ``[2][ld_x]``; block 0 of the messages decodes to g and block 1 to u, ``G = gs g + l2c
+    beta`` and ``H dir = gs u + l2c dir``.  A gradient round (phase 0) starts linear CG on ``H x = -G`` and writes
+    ``[beta ; dir]`` to beta_w; a CG round takes one step and either writes the next direction or ends the outer
+    iteration with ``beta += tau x`` (``beta -= eta G`` where CG could not start or take a first step) and writes
+    ``[beta' ; 0]``.  hist takes ``[beta' ; 0]`` in every round.  Native on GPU tensors; on CPU tensors a NumPy twin of
+    the same recurrences."""
+    ld_x, d_x, J, xi, tau = int(ld_x), int(d_x), int(J), float(xi), float(tau)
+    if not (1 <= d_x <= ld_x and beta.numel() == 2 * ld_x):
+        raise ValueError(f"newton_cg_update: two blocks of {ld_x} columns do not describe this model")
+    if tuple(state.shape) != (5, ld_x) or state.dtype != torch.float64 or scal.numel() != 2 or \
+            scal.dtype != torch.float64 or phase.numel() != 4 or phase.dtype != torch.int32:
+        raise ValueError(f"newton_cg_update: state must be float64 [5, {ld_x}], scal float64 [2] and phase int32 [4]")
+    if not 1 <= J <= NEWTON_MAX_INNER:
+        raise ValueError(f"newton_cg_update: J must be in 1..{NEWTON_MAX_INNER}, got {J}")
+    for name, v in (("tolerance", xi), ("step", tau)):
+        if not (v > 0.0 and v != float("inf")):
+            raise ValueError(f"newton_cg_update: the {name} must be finite and > 0, got {v}")
+    if beta.is_cuda:
+        C = native()
+        if len(msgs) > C.MAX_MSGS:
+            raise ValueError(f"at most {C.MAX_MSGS} messages per combine")
+        C.newton_cg_update(list(msgs), [float(c) for c in coefs], beta, hist, beta_w, state, scal, phase, ld_x, d_x, J,
+                           float(eta), float(gs), float(l2c), xi, tau, gate)
+        return
+    if gate is not None and int(gate.reshape(-1)[0]) != 0:
+        return
+    st, sc, ph, b = state.numpy(), scal.numpy(), phase.numpy(), beta.numpy()[:d_x].copy()
+    g, u = np.zeros(d_x), np.zeros(d_x)
+    for m, c in zip(msgs, coefs):
+        g += float(c) * m[:d_x].double().numpy()
+        u += float(c) * m[ld_x: ld_x + d_x].double().numpy()
+    x, r, dr, G0 = (st[k, :d_x] for k in range(4))
+    cg, inner, nd = ph[0] == 1, (int(ph[1]) if ph[0] == 1 else 0), np.zeros(d_x)
+    ok = lambda v: bool(np.isfinite(v) and v > 0)  # noqa: E731
+    with np.errstate(all="ignore"):
+        if not cg:
+            G0[:] = gs * g + l2c * b
+            rs = float(G0.dot(G0))
+            if ok(rs):
+                mode, sc[:] = 0, rs
+                x[:], r[:], dr[:] = 0.0, -G0, -G0
+            else:
+                mode = 6
+        else:
+            Hv = gs * u + l2c * dr
+            kappa = float(dr.dot(Hv))
+            if not ok(kappa):
+                mode = 5 if inner == 0 else 4
+            else:
+                a = sc[0] / kappa
+                x += a * dr
+                r -= a * Hv
+                rs, inner = float(r.dot(r)), inner + 1
+                mode = 2 if not rs > xi * xi * sc[1] else 3 if inner >= J else 1
+                if mode == 1:
+                    dr[:] = r + (rs / sc[0]) * dr
+                    sc[0] = rs
+        if mode in (0, 1):
+            nb, nd = b, dr.copy()
+        else:
+            nb = b - eta * G0 if mode >= 5 else b + tau * x
+    ph[:] = (int(mode in (0, 1)), inner, mode, int(ph[3]) + int(mode not in (0, 1)))
+    new = torch.from_numpy(nb)
+    beta[:d_x] = new
+    if hist is not None:
+        hist[:d_x] = new
+        hist[ld_x:] = 0.0
+    if beta_w is not None:
+        beta_w.zero_()
+        beta_w[:d_x] = new.to(beta_w.dtype)
+        beta_w[ld_x: ld_x + d_x] = torch.from_numpy(nd).to(beta_w.dtype)
+
+
 def _update_blocked(name, msgs, coefs, beta, u, block_ld, d_x, decay, gm, l2, thr, theta, rule, hist, beta_w,
                     g_out) -> None:
     """The two blocked forms: ``thr`` None is combine_update_blocks, a sequence is combine_update_prox."""

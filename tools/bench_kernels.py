@@ -165,6 +165,7 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
     from erasurehead_amd.ops.cv import CvGradPlan
     from erasurehead_amd.ops.ovr import OvrGradPlan
     from erasurehead_amd.ops.precond import PrecondGradPlan
+    from erasurehead_amd.ops.hvp import HvpGradPlan
 
     layouts = {"naive": [[p] for p in range(8)], "agc": [[0, 1, 2]] * 3 + [[3, 4, 5]] * 3 + [[6, 7]] * 2}
     if layouts_only:
@@ -229,6 +230,20 @@ def sweep_cases(out, ds=(256, 1000, 2048, 4096), ns=(100_000, 1_000_000, 4_000_0
                             ms = _time(lambda: plan.run(b2, G), reps=20)
                             distinct = 8 * nbytes / 1e12  # TB
                             r = {"kernel": "grad_curv_sweep", "precision": prec_name, "d": d, "n": n, "layout": lay,
+                                 "loss": "logistic", "tasks": plan.ntasks, "ms": ms, "distinct_TBps": distinct / ms * 1e3,
+                                 "copy_TBps": ceiling, "frac": distinct / ms * 1e3 / ceiling}
+                            out.append(r)
+                            print(json.dumps(r), flush=True)
+                            del plan, G
+                            continue
+                        if loss == "hvp":  # gradient + Hessian-vector product of one model: hold against precond
+                            plan = HvpGradPlan([[(p, 1.0) for p in m] for m in msgs], parts, prec,
+                                               LOSS_NAMES["logistic"], d)
+                            b2 = torch.randn(plan.ld, device="cuda", dtype=prec.acc) * 0.01
+                            G = plan.out_buffer()[0]
+                            ms = _time(lambda: plan.run(b2, G), reps=20)
+                            distinct = 8 * nbytes / 1e12  # TB
+                            r = {"kernel": "grad_hvp_sweep", "precision": prec_name, "d": d, "n": n, "layout": lay,
                                  "loss": "logistic", "tasks": plan.ntasks, "ms": ms, "distinct_TBps": distinct / ms * 1e3,
                                  "copy_TBps": ceiling, "frac": distinct / ms * 1e3 / ceiling}
                             out.append(r)
@@ -444,6 +459,9 @@ def main():
     ap.add_argument("--precond", action="store_true",
                     help="--only sweep: also run the preconditioned run's kernel (grad_curv: gradient + Hessian "
                          "diagonal of one logistic model), to hold against --loss multimodel --models 2")
+    ap.add_argument("--hvp", action="store_true",
+                    help="--only sweep: also run the Newton-CG run's kernel (grad_hvp: gradient + Hessian-vector product "
+                         "of one logistic model), to hold against --precond and --loss logistic")
     ap.add_argument("--weighted", action="store_true",
                     help="--only sweep / sparse: the weighted code of the loss on labels y * w, w = 10**U(-2, 2) (logistic, "
                          "squared_hinge; sparse: logistic) -- compare with a run without the flag")
@@ -479,9 +497,11 @@ def main():
         losses += ("cv",)
     if a.precond and "precond" not in losses:  # (may also be named in --loss, to alternate it with the other kernels)
         losses += ("precond",)
-    if any(x not in LOSS_CHOICES and x not in ("multimodel", "ovr", "cv", "precond") for x in losses):
-        ap.error(f"--loss: names from {sorted(LOSS_CHOICES) + ['multimodel', 'ovr', 'cv', 'precond']}")
-    if a.weighted and any(x in ("least_squares", "softmax", "multimodel", "ovr", "cv", "precond") for x in losses):
+    if a.hvp and "hvp" not in losses:
+        losses += ("hvp",)
+    if any(x not in LOSS_CHOICES and x not in ("multimodel", "ovr", "cv", "precond", "hvp") for x in losses):
+        ap.error(f"--loss: names from {sorted(LOSS_CHOICES) + ['multimodel', 'ovr', 'cv', 'precond', 'hvp']}")
+    if a.weighted and any(x in ("least_squares", "softmax", "multimodel", "ovr", "cv", "precond", "hvp") for x in losses):
         ap.error("--weighted: logistic or squared_hinge (no other kernel has a weighted instance)")
     out = []
     if a.only in (None, "dense"):
