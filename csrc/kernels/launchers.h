@@ -231,6 +231,22 @@ constexpr int kEvalClassCols = 112;
 hipError_t eval_classes_launch(int x_dtype, int mode, const void* X, long long ldx, long long n, int d, const void* y,
                                const void* B, int ldb, int R, int C, double* loss, double* hits, hipStream_t st);
 
+// ---- exact ROC AUC pair counts (auc.hip) -----------------------------------------------------
+// sums[j] = sum over the rows q of rows_query of #{s in rows_sorted : P[s][j] < P[q][j]} + #{s : P[s][j] <= P[q][j]}
+// for the ncols first columns of P [n, ldp] (p_dtype 0 fp64 / 1 fp32; -0.0 == +0.0), flags[j] = 1 iff a score of
+// column j is NaN (sums[j] is then meaningless), else 0.  rows_sorted [m] / rows_query [nq]: row indices, int32 or
+// int64 (idx64), every one in [0, n): checked by the caller.  T: sorted keys per workgroup, a power of two <=
+// kAucMaxTile (T * 8 bytes of LDS).  Scratch: S [ncols * auc_tiles(m, T) * T], Q [ncols * nq], part
+// [ncols * auc_tiles(m, T)].  m or nq < 1, m + nq >= 2^31, ncols > 65535 or a grid past 2^31 threads is
+// hipErrorInvalidValue and launches nothing; ncols == 0 launches nothing.
+constexpr int kAucTile = 16384;  // 128 KiB of LDS: measured against 2048 .. 8192 (docs/PERF_NOTES.md)
+constexpr int kAucMaxTile = 16384;
+inline long long auc_tiles(long long m, int T) { return (m + T - 1) / T; }
+hipError_t auc_pair_sums_launch(int p_dtype, int idx64, const void* P, long long ldp, const void* rows_sorted,
+                                long long m, const void* rows_query, long long nq, int ncols, int T,
+                                unsigned long long* S, unsigned long long* Q, unsigned long long* part,
+                                long long* sums, int* flags, hipStream_t st);
+
 // ---- post-hoc evaluation over CSR / one-hot rows (eval_sparse.hip) ---------------------------
 // Bt: betas transposed [ld, R] (R <= 256); vals == nullptr: pattern-only; dtype 0 fp64, 1 fp32
 hipError_t eval_csr_loss_launch(int dtype, int loss_kind, const long long* row_ptr, const int* col, const void* vals,

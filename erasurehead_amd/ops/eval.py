@@ -3,8 +3,8 @@
 Dense data: the MFMA GEMM P = X B^T with the loss reduction fused in its epilogue
 (csrc/kernels/eval.hip), streamed partition by partition so the training set never
 has to be resident at once.  Test predictions are materialised for the ROC AUC, which
-is a rank statistic computed on the device with a sort per round (ties count 1/2, i.e.
-exactly sklearn's trapezoidal roc_curve + auc).
+is a rank statistic computed on the device from exact integer pair counts (csrc/kernels/auc.hip: an LDS tile sort of
+one class, binary-search counts of the other; ties count 1/2, i.e. exactly sklearn's trapezoidal roc_curve + auc).
 Sparse data (the reference's one-hot real datasets): the hand-written CSR kernel
 (csrc/kernels/eval_sparse.hip) gathers rows of the transposed betas Bt [ld, R] per non-zero and
 fuses the same loss epilogue; pattern-only rows (every value 1) carry no value array.  CPU
@@ -212,24 +212,67 @@ def loss_sums(chunks: Iterable[Tuple[object, torch.Tensor]], B: torch.Tensor, d:
 
 
 def warm_auc(device) -> None:
-    """Load the code objects of the AUC path (torch's segmented sort, scans, index_add) once.
+    """One tiny auc_columns call on ``device``: the first use of the AUC path in a process.
 
-    Measured (profiles/round2/s1_eval): the first auc_columns call of a process costs 0.6 s, all of it
-    first-use code-object loading (the same call warm: 4.5 ms for 100 x 2e5).  The trainer runs
-    this on the master while it generates / loads the training data, so the post-hoc evaluation
-    does not pay it."""
+    On the GPU that is the native pair-count kernels (csrc/kernels/auc.hip), whose code object comes with the library,
+    and torch's nonzero; the torch sort path it replaced cost 0.6 s of first-use code-object loading
+    (profiles/round2/s1_eval; docs/PERF_NOTES.md has both figures).  The trainer runs this on the master while it
+    generates / loads the training data, so the post-hoc evaluation does not pay it."""
     y = torch.tensor([1.0, -1.0, 1.0, -1.0], dtype=torch.float64, device=device)
     P = torch.tensor([[0.1, 0.2], [0.3, 0.1], [0.3, 0.4], [0.0, 0.4]], dtype=torch.float64, device=device)
     auc_columns(y, P)
 
 
-def auc_columns(y: torch.Tensor, P: torch.Tensor, chunk: int = 0) -> np.ndarray:
-    """ROC AUC of every column of P against labels y in {-1, +1} (ties count 1/2).
+# The native count does tiles * queries searches per column (tiles = ceil(sorted class / AUC_TILE)), the torch path
+# work that grows with n log n.  Measured on an MI355X at R = 100, balanced classes, tile 16384 (docs/PERF_NOTES.md "AUC
+# pair count"): native 22.1 ms against torch 38.1 ms at n = 1e6 (tiles * queries = 15.5 n), 78.7 ms against 57.4 ms at
+# n = 2e6 (31 n).  The native path is taken up to the largest ratio at which it was measured faster.
+_AUC_NATIVE_MAX_SEARCHES_PER_ROW = 16
 
-    Batched Mann-Whitney U over all columns at once (sklearn's trapezoidal roc_curve + auc is
-    the same statistic): one column-wise sort, tie groups found by comparing neighbours, the
-    average rank of each tie group via a segmented scatter-add, one reduction per column.
-    No per-column host synchronisation; ``chunk`` bounds the columns per pass (memory).
+
+def _auc_native_pays(n_pos: int, n_neg: int) -> bool:
+    tiles = -(-min(n_pos, n_neg) // native().AUC_TILE)
+    return tiles * max(n_pos, n_neg) <= _AUC_NATIVE_MAX_SEARCHES_PER_ROW * (n_pos + n_neg)
+
+
+def _auc_native(pos: torch.Tensor, P: torch.Tensor, n_pos: int, n_neg: int, chunk: int, out: np.ndarray) -> None:
+    """auc_columns on GPU tensors: exact integer pair counts from csrc/kernels/auc.hip, one division per column.
+
+    The smaller class is the one the kernel sorts (its work is queries x ceil(sorted / tile) searches).  With the
+    negatives sorted the kernel's sum is U2 = sum_p 2 #{neg < p} + #{neg == p}; with the positives sorted it is
+    2 n+ n- - U2.  A column the kernel flags holds a NaN: its value depends on torch's NaN ordering, so that column
+    alone goes through the torch path."""
+    C = native()
+    if P.dtype not in (torch.float64, torch.float32):
+        P = P.double()
+    if P.stride(1) != 1:
+        P = P.contiguous()
+    rows_pos, rows_neg = torch.nonzero(pos).squeeze(1), torch.nonzero(~pos).squeeze(1)
+    neg_sorted = n_neg <= n_pos
+    rows_sorted, rows_query = (rows_neg, rows_pos) if neg_sorted else (rows_pos, rows_neg)
+    pairs2 = 2 * n_pos * n_neg
+    R = P.shape[1]
+    for c0 in range(0, R, chunk):
+        k = min(chunk, R - c0)
+        sums = torch.empty(k, dtype=torch.int64, device=P.device)
+        flags = torch.empty(k, dtype=torch.int32, device=P.device)
+        C.auc_pair_sums(P[:, c0:c0 + k], rows_sorted, rows_query, k, sums, flags)
+        s = sums.cpu().numpy()
+        u2 = s if neg_sorted else pairs2 - s
+        out[c0:c0 + k] = u2.astype(np.float64) / (2.0 * n_pos * n_neg)
+        for j in np.nonzero(flags.cpu().numpy())[0]:
+            _auc_torch(pos, P[:, c0 + j:c0 + j + 1], n_pos, n_neg, 1, out[c0 + j:c0 + j + 1])
+
+
+def auc_columns(y: torch.Tensor, P: torch.Tensor, chunk: int = 0) -> np.ndarray:
+    """ROC AUC of every column of P against labels y in {-1, +1} (ties count 1/2; sklearn's trapezoidal
+    roc_curve + auc is the same statistic).  ``chunk`` bounds the columns per pass (memory: the default keeps
+    chunk * n at 2^26 elements).
+
+    GPU tensors: the native pair count (:func:`_auc_native`), exact in integers.  CPU tensors, and a GPU column that
+    holds a NaN: batched Mann-Whitney U in torch (:func:`_auc_torch`).  The native count's work grows with the product
+    of the class sizes: GPU tensors with ceil(smaller class / 16384) * larger class > 16 n (balanced classes: beyond
+    about 1e6 rows) stay on the torch path, which was measured faster there (:func:`_auc_native_pays`).
     """
     y = y.to(P.device)
     pos = (y == 1)
@@ -242,6 +285,14 @@ def auc_columns(y: torch.Tensor, P: torch.Tensor, chunk: int = 0) -> np.ndarray:
         return out
     if chunk <= 0:
         chunk = max(1, min(R, (1 << 26) // max(1, n)))
+    (_auc_native if P.is_cuda and _auc_native_pays(n_pos, n_neg) else _auc_torch)(pos, P, n_pos, n_neg, chunk, out)
+    return out
+
+
+def _auc_torch(pos: torch.Tensor, P: torch.Tensor, n_pos: int, n_neg: int, chunk: int, out: np.ndarray) -> None:
+    """One column-wise sort, tie groups found by comparing neighbours, the average rank of each tie group via a
+    segmented scatter-add, one reduction per column; no per-column host synchronisation."""
+    n, R = P.shape
     ar = torch.arange(1, n + 1, dtype=torch.float64, device=P.device)
     for c0 in range(0, R, chunk):
         S = P[:, c0:c0 + chunk].double().t().contiguous()  # [m, n]: every scan runs along contiguous memory
@@ -258,4 +309,3 @@ def auc_columns(y: torch.Tensor, P: torch.Tensor, chunk: int = 0) -> np.ndarray:
         avg = (ssum / scnt.clamp(min=1))[flat].view(m, n)  # average rank of every element
         u = (avg * pos_s).sum(1) - n_pos * (n_pos + 1) / 2.0
         out[c0:c0 + m] = (u / (n_pos * n_neg)).cpu().numpy()
-    return out
