@@ -6,11 +6,13 @@ Block 0 of a message (the gradient) is held to tests/numerics.py oracle_message 
     K_HVP u sum_p |c_p| sum_i (|w_i q_i| + w_i sum_k |x_ik v_k| + L |q_i| sum_k |x_ik beta_k|) |x_ij| + tiny sum_p |c_p| sum_i |x_ij|:
 the accumulation of X^T (w q), then the error of the dot product q carried through w, then that of z carried through
 the curvature (L its Lipschitz constant in z: 1 / (6 sqrt 3) logistic, 0 least squares; squared hinge is piecewise
-constant and the oracle asserts that no row lies within K u sum_k |x_ik beta_k| of its jump)."""
+constant and the oracle asserts that no row lies within K u sum_k |x_ik beta_k| of its jump).  The oracle, hvp_oracle,
+lives in tests/newton_edge_cases.py.  K_HVP below was measured on the kernel itself; the stage-edge tests of
+tests/test_newton_edges_gpu.py hold block 1 to K_HVP_EDGE, which follows the rule at the top of tests/numerics.py (the
+plain torch path on CPU tensors, times 8, rounded up to a power of two)."""
 import numpy as np
 import pytest
 import torch
-from scipy.special import expit
 
 from erasurehead_amd.engine import Trainer
 from erasurehead_amd.models import losses
@@ -20,7 +22,8 @@ from erasurehead_amd.ops.update import newton_cg_update, newton_state
 from erasurehead_amd.parallel.dist import DistEnv
 import block_edge_cases as bc
 import numerics as nx
-from numerics import LD, LEAST_SQUARES, LOGISTIC, LOSS_IDS, LOSSES, SQUARED_HINGE
+from newton_edge_cases import hvp_oracle
+from numerics import LD, LOSS_IDS, LOSSES
 from test_lbfgs_cpu import check_step, rel
 from test_multimodel_cpu import arrival_sets, make
 
@@ -50,27 +53,6 @@ def inputs(d, prec_name):
         v[:d] = torch.from_numpy(rng.randn(d) * 10.0 ** rng.uniform(-3.0, 1.0, d) / np.sqrt(d)).to(prec.acc)
         _inputs[(d, prec_name)] = (parts, host, beta, bh, v, v[:d].double().numpy())
     return _inputs[(d, prec_name)]
-
-
-def hvp_oracle(loss, segments, host, bh, vh, prec, k):
-    """(u [d], per-column bound [d]) of block 1 of one message in long double; asserts the squared-hinge margin."""
-    d = len(bh)
-    u, acc, tiny = np.zeros(d, LD), np.zeros(d, LD), np.zeros(d, LD)
-    b, v = np.asarray(bh, LD), np.asarray(vh, LD)
-    for p, coef in segments:
-        X, y = np.asarray(host[p][0], LD), np.asarray(host[p][1], LD)
-        z, az, q, aq = X @ b, np.abs(X) @ np.abs(b), X @ v, np.abs(X) @ np.abs(v)
-        if loss == LOGISTIC:
-            s = expit(-(y * z))
-            w, lip = s * (1 - s), LD(1) / (6 * np.sqrt(LD(3)))
-        else:
-            w, lip = (np.full_like(z, 2) if loss == LEAST_SQUARES else np.where(y * z < 1, LD(2), LD(0))), LD(0)
-        if loss == SQUARED_HINGE:
-            assert np.all(np.abs(1 - y * z) > nx.K * nx.acc_eps(prec) * az), "a row sits on the squared hinge's jump"
-        u += LD(coef) * (X.T @ (w * q))
-        acc += abs(coef) * (np.abs(X).T @ (np.abs(w * q) + w * aq + lip * np.abs(q) * az))
-        tiny += abs(coef) * np.abs(X).sum(0)
-    return u, LD(k * nx.acc_eps(prec)) * acc + LD(nx.acc_tiny(prec)) * tiny
 
 
 @pytest.mark.parametrize("prec_name", bc.SCALAR_PRECS)
